@@ -24,12 +24,23 @@ Every config keeps BASELINE.json's client count (4 / 32 / 128 / 512 / 64;
   --weak                  round 2's weak scaling: every rank gets the
                           config's K clients of its own.
 
-    python bench.py                       # 1 GPU, default steps
+    python bench.py                       # 1 GPU, default steps: the headline alone
+    python bench.py --full                # ... and the cpu_baseline leg (multi-GPU: the nested legs)
+    python bench.py --dump-outputs DIR    # ... and the last timed step's results as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8
     python bench.py --gpus 8              # the same: bench.py spawns the 8 ranks itself
 
-Nested legs of a multi-GPU --mode param FedAvg line (each its own JSON object):
+A plain run sets up, warms up, times --steps steps and prints the line.  What
+else the benchmark measures runs only with --full: the cpu_baseline leg at one
+GPU, the nested legs over several.  --dump-outputs DIR writes what the timed
+path computed in its last step (the arrays its caller reads: the per-dtype
+averages, the median row, the Krum distance matrix, ...) as float32 / float64
+.npy files, whole or as a fixed seeded sample (DUMP_BUDGET_BYTES in all); the
+inputs are seeded, so two builds can be compared output for output.
+
+Nested legs of a multi-GPU --mode param FedAvg line with --full (each its own
+JSON object):
 
   exchange      north_star's client axis on the same clients: fp32 partials +
                 the chunked RCCL reduce-scatter over xGMI (--no-exchange skips)
@@ -61,8 +72,8 @@ line.  FEDAGG_BENCH_FAIL / FEDAGG_BENCH_HANG ("<leg>:<rank>,...") inject a
 failure or a hang into a leg's handshake (tests/test_bench_legs.py, with
 --probe-cpu: the same orchestration with host stand-in reductions on gloo).
 
-Prints ONE JSON line on rank 0 (contract in the task statement); at N = 1 the
-cpu_baseline leg times the reference's own CPU loop (oracle/cpu_baseline.py)
+Prints ONE JSON line on rank 0 (contract in the task statement); at N = 1 with
+--full the cpu_baseline leg times the reference's own CPU loop (oracle/cpu_baseline.py)
 over the FULL workload (every key, every client) at the job's CPU quota and
 at one thread.  `--op median` lines also carry roofline.valu: the median's
 sorting networks are bound by VALU issue above ~128 clients, so the executed
@@ -158,7 +169,13 @@ def parse(argv=None):
     ap.add_argument("--clients", type=int, default=None,
                     help="1 GPU: clients per GPU instead of the config's (e.g. config 4's median over all 512 "
                          "clients: the median does not split along the client axis)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the cpu_baseline leg (1 GPU) and the nested legs (multi-GPU "
+                         "--mode param); a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of outputs too large for DUMP_BUDGET_BYTES)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full at 1 GPU: skip the cpu_baseline leg")
     ap.add_argument("--no-exchange", action="store_true",
                     help="multi-GPU --mode param: skip the nested client-axis (RCCL reduce-scatter) measurement")
     ap.add_argument("--cpu-reps", type=int, default=5, help="cpu_baseline: timed runs after one warm-up")
@@ -174,7 +191,10 @@ def parse(argv=None):
     ap.add_argument("--watchdog-s", type=float, default=None, help=argparse.SUPPRESS)  # default: budget + 60 s
     ap.add_argument("--spawn-probe", action="store_true", help=argparse.SUPPRESS)  # CPU test of the self-launch
     ap.add_argument("--probe-cpu", action="store_true", help=argparse.SUPPRESS)  # CPU test of the orchestration
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def free_port() -> int:
@@ -682,6 +702,54 @@ def load_median_valu(config: str, mode: str, world: int, variant: str, clients: 
         return None
 
 
+# ---- --dump-outputs -------------------------------------------------------------------------------------------------
+
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs together (the arrays; .npy headers are ~128 B each)
+DUMP_SEED = 20240  # the sample's element indices depend on this seed and the array's shape alone
+
+
+def _dtype_name(dt) -> str:
+    return str(dt).replace("torch.", "")
+
+
+def _dump_sample(t: torch.Tensor, count: int, seed: int) -> torch.Tensor:
+    """``count`` elements of ``t`` at seeded random flat positions (sorted, drawn
+    with replacement on the host, so the same shape gives the same positions
+    in every run and build), gathered on t's device."""
+    g = torch.Generator().manual_seed(seed)
+    flat = torch.randint(0, t.numel(), (count,), generator=g, dtype=torch.int64).sort().values.to(t.device)
+    index = []
+    for size in reversed(t.shape):  # flat position -> one index per dimension (t may be a strided view)
+        index.append(flat % size)
+        flat = flat // size
+    return t[tuple(reversed(index))]
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank=None, world: int = 1) -> None:
+    """Write the timed path's results as <out_dir>/<name>.npy (<name>.rank<r>.npy
+    per rank of a multi-GPU run): float64 for float64 and integer results,
+    float32 for the rest.  Results that fit this rank's budget together
+    (DUMP_BUDGET_BYTES over the ranks) are written whole; otherwise every array
+    gets an equal share of it, and an array over its share is written as a
+    fixed sample (_dump_sample)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        items.append((name, t, torch.float64 if wide else torch.float32, 8 if wide else 4))
+    share = DUMP_BUDGET_BYTES // world
+    if sum(t.numel() * size for _, t, _, size in items) > share:
+        share //= len(items)
+    for i, (name, t, dt, size) in enumerate(items):
+        if t.numel() * size > share:
+            t = _dump_sample(t, share // size, DUMP_SEED + i)
+        safe = "".join(c if c.isalnum() or c in "._-" else "_" for c in name)
+        path = os.path.join(out_dir, safe + (f".rank{rank}" if rank is not None else "") + ".npy")
+        np.save(path, t.detach().to(dt).cpu().numpy())
+
+
 # ---- timing ---------------------------------------------------------------------------------------------------------
 
 
@@ -850,6 +918,7 @@ def client_axis_step(bucket, dom_dt, w_local, chunks: int, world: int):
             if dt in (torch.bfloat16, torch.float16):
                 agg.shard_in_model_dtype()  # the one rounding of a 16-bit model, after the exchange
 
+    step.aggs = aggs  # the shards a caller reads after a step (--dump-outputs)
     gd = bucket.groups[dom_dt]
     dom_bytes = gd.rows.shape[0] * gd.length * gd.rows.element_size() + gd.length * 4  # rows in, fp32 partial out
     xgmi_bytes = (world - 1) * aggs[dom_dt].piece * len(aggs[dom_dt].bounds) * 4
@@ -1200,6 +1269,7 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
         def step(ev=None, cev=None):
             sharded_opt.aggregate(w_local, events=ev, comm_events=cev)
 
+        result = lambda: {"param_shard": sharded_opt.param}  # noqa: E731
         n_launch = len(sharded_opt.agg.bounds)
         leg.ready()
         sharded_opt.aggregate(w_local)  # first step (no state read) before timing
@@ -1212,6 +1282,7 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
         def step(ev=None, cev=None):
             server.aggregate(events=ev)
 
+        result = server.get_global_model_params
         n_launch = 1
         server.aggregate()  # first step (no momentum read) happens before timing
         dom_bytes = server.algorithmic_bytes()
@@ -1230,6 +1301,7 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
             if ev is not None:
                 ev[1].record()
 
+        result = lambda: {"median": med_out[:gd.length]}  # noqa: E731
         n_launch = 1
         dom_bytes = (K + 1) * gd.length * gd.rows.element_size()
     elif a.op == "rlr":
@@ -1250,6 +1322,7 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
             if ev is not None:
                 ev[1].record()
 
+        result = lambda: {"rlr": rlr_out[:gd.length]}  # noqa: E731
         n_launch = 1
         dom_bytes = (K + 1) * gd.length * 4
     elif a.op == "mpi":
@@ -1275,6 +1348,7 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
             if ev is not None:
                 ev[1].record()
 
+        result = lambda: {"mpi": mpi_out[:gd.length]}  # noqa: E731
         n_launch = 1
         dom_bytes = K * gd.length * gd.rows.element_size() + gd.length * torch.empty((), dtype=gd.out_dtype).element_size()
     elif a.op in ("krum", "dist2", "clip"):
@@ -1329,6 +1403,8 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
             if ev is not None:
                 ev[1].record()
 
+        result = {"krum": lambda: {"pair_dist2": pd_out}, "dist2": lambda: {"dist2": d_out},
+                  "clip": lambda: {"clipped": clip_out[:, :gd.length]}}[a.op]
         n_launch = 1
     elif a.op in ("secagg", "lsa"):
         from fedml_amd import _native as nat
@@ -1340,7 +1416,8 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
                                                         sec_out.data_ptr(), nat.FEDAGG_ALIGNED16, nat.stream_handle())
             dom_bytes = (K + 1) * gd.length * 8
         else:
-            mask = torch.empty(gd.padded, dtype=torch.int64, device=dev).random_(0, LSA_PRIME)
+            mask = torch.empty(gd.padded, dtype=torch.int64, device=dev).random_(
+                0, LSA_PRIME, generator=torch.Generator(device=dev).manual_seed(1000 * rank + 999))
             sec_out = torch.empty(gd.padded, dtype=torch.float32, device=dev)
             call = lambda: nat.lib().fedagg_lsa_reconstruct_f32(  # noqa: E731
                 gd.d_ptrs.data_ptr(), K, gd.length, mask.data_ptr(), LSA_PRIME, LSA_QBITS, 1.0 / K,
@@ -1354,6 +1431,7 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
             if ev is not None:
                 ev[1].record()
 
+        result = lambda: {a.op: sec_out[:gd.length]}  # noqa: E731
         n_launch = 1
     elif mode in ("single", "param"):
         # one GPU, or this rank's whole-key shard of every client: the
@@ -1364,12 +1442,15 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
         def step(ev=None, cev=None):
             bucket.reduce_into(outs, w, events={dom_dt: ev} if ev is not None else None)
 
+        result = lambda: {f"fedavg_{_dtype_name(dt)}": outs[dt][:g.length] for dt, g in groups}  # noqa: E731
         n_launch = 1
         gd = bucket.groups[dom_dt]
         dom_bytes = K_loc * gd.length * gd.rows.element_size() + \
             gd.length * torch.empty((), dtype=gd.out_dtype).element_size()
     else:  # client axis: this rank's clients' partial + chunked RCCL reduce-scatter
         step, n_launch, dom_bytes, xgmi_bytes = client_axis_step(bucket, dom_dt, w_local, a.chunks, world)
+        result = lambda: {f"shard_{_dtype_name(dt)}": agg.shard_in_model_dtype()  # noqa: E731
+                          for dt, agg in step.aggs.items()}
         leg.ready()
 
     timed_comm = mode == "client" and world > 1 and a.backend == "nccl"
@@ -1378,6 +1459,8 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
     hbm_all = dom_bytes / (elapsed / a.steps) / 1e9  # this rank's algorithmic bytes over the step time
     if world > 1:
         elapsed, achieved, hbm_all, comm_ms = over_ranks(leg, elapsed, achieved, hbm_all, comm_ms)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, result(), rank if world > 1 else None, world)
 
     ms_per_step = elapsed / a.steps * 1e3
     gram_op = a.op == "krum" and (a.pair_distance == "gram" or (a.pair_distance == "auto" and K <= 128))
@@ -1478,7 +1561,7 @@ def measure_headline(a, world: int, rank: int, dev, coord: Coord):
                                 "comm_ms_per_step": round(comm_ms, 4) if comm_ms is not None else None,
                                 "note": "comm_ms: mean over ranks of the chunks' reduce-scatter time on the comm "
                                         "stream (overlapping the next chunk's reduction)"}
-    keep = (bucket, ns_local) if world == 1 and a.op == "fedavg" and not a.no_cpu_baseline else None
+    keep = (bucket, ns_local) if a.full and world == 1 and a.op == "fedavg" and not a.no_cpu_baseline else None
     return line, keep
 
 
@@ -1600,7 +1683,7 @@ def main():
             line, keep = measure_headline(a, world, rank, dev, coord)
         if rank == 0:
             REPORT.line = line
-        if world > 1 and a.mode == "param" and a.op == "fedavg" and not a.fedopt:
+        if a.full and world > 1 and a.mode == "param" and a.op == "fedavg" and not a.fedopt:
             try:
                 run_nested(a, world, rank, dev, coord, budget, line)
             except Exception as e:  # noqa: BLE001 -- the headline stands whatever the nested legs hit

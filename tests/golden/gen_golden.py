@@ -165,7 +165,27 @@ def save(name: str, meta: dict, arrays: dict) -> None:
     os.makedirs(OUT_DIR, exist_ok=True)
     payload = {f"a{i}": v for i, v in enumerate(arrays.values())}
     meta["array_names"] = list(arrays.keys())
-    np.savez_compressed(os.path.join(OUT_DIR, f"{name}.npz"), meta=np.array(json.dumps(meta)), **payload)
+    write_parts(os.path.join(OUT_DIR, f"{name}.npz"), np.array(json.dumps(meta)), payload)
+
+
+MAX_FILE_BYTES = 1 << 20  # no committed file is larger
+
+
+def write_parts(path: str, meta: np.ndarray, payload: dict) -> None:
+    """One archive while it stays within MAX_FILE_BYTES; else the arrays dealt
+    in order over the fewest files that do: <path> (with meta) and
+    <path>.part1, .part2, ... (tests/golden_util.load reads them back as one)."""
+    keys = list(payload)
+    for n in range(1, len(keys) + 1):
+        per = -(-len(keys) // n)
+        names = [path] + [f"{path}.part{i}" for i in range(1, n)]
+        for i, p in enumerate(names):
+            part = {k: payload[k] for k in keys[i * per:(i + 1) * per]}
+            with open(p, "wb") as f:  # a file object: savez would append ".npz" to a part's name
+                np.savez_compressed(f, **({"meta": meta} if i == 0 else {}), **part)
+        if all(os.path.getsize(p) <= MAX_FILE_BYTES for p in names):
+            return
+    raise ValueError(f"{path}: one array alone exceeds {MAX_FILE_BYTES} bytes")
 
 
 def run_agg_case(FedMLAggOperator, spec, aggregate=None):

@@ -23,9 +23,16 @@ def fixture_names(prefix: str = "") -> List[str]:
 
 
 def load(name: str) -> Tuple[dict, Dict[str, np.ndarray]]:
-    with np.load(os.path.join(FIX_DIR, f"{name}.npz"), allow_pickle=False) as z:
-        meta = json.loads(str(z["meta"]))
-        arrays = {n: z[f"a{i}"] for i, n in enumerate(meta["array_names"])}
+    """A fixture's meta and arrays.  A fixture too large for one committed file
+    continues in <name>.npz.part1, .part2, ... (gen_golden.save): the same
+    archive format, each holding the next run of arrays."""
+    path = os.path.join(FIX_DIR, f"{name}.npz")
+    members = {}
+    for p in [path] + sorted(glob.glob(glob.escape(path) + ".part*"), key=lambda q: int(q.rsplit(".part", 1)[1])):
+        with np.load(p, allow_pickle=False) as z:
+            members.update((k, z[k]) for k in z.files)
+    meta = json.loads(str(members["meta"]))
+    arrays = {n: members[f"a{i}"] for i, n in enumerate(meta["array_names"])}
     return meta, arrays
 
 

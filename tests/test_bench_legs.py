@@ -2,7 +2,8 @@
 `--probe-cpu` runs the real coordination (host-store barriers and timing
 gathers, the readiness handshake, the budget, the watchdog, the nested legs
 and the JSON line) with host stand-in reductions over gloo, and the
-FEDAGG_BENCH_FAIL / FEDAGG_BENCH_HANG hooks break one rank on purpose."""
+FEDAGG_BENCH_FAIL / FEDAGG_BENCH_HANG hooks break one rank on purpose.  The
+nested legs run only with --full, so every run here passes it."""
 import json
 import os
 import subprocess
@@ -12,15 +13,15 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(args, env=None, timeout=120):
+def _run(args, env=None, timeout=120, full=True):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "FEDAGG_BENCH_FAIL", "FEDAGG_BENCH_HANG"):
         e.pop(k, None)
     e.update(env or {})
     t0 = time.monotonic()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--probe-cpu", "--backend", "gloo",
-                        "--steps", "3", "--warmup", "1"] + args, capture_output=True, text=True, timeout=timeout,
-                       env=e, cwd=ROOT)
+                        "--steps", "3", "--warmup", "1"] + (["--full"] if full else []) + args,
+                       capture_output=True, text=True, timeout=timeout, env=e, cwd=ROOT)
     lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
     return p, lines, time.monotonic() - t0
 
@@ -36,6 +37,15 @@ def test_all_legs_run_and_one_line_is_printed():
         assert "error" not in obj and "skipped" not in obj, obj
         assert obj["ms_per_step"] > 0
     assert line["exchange"]["backend"] == "gloo"
+
+
+def test_a_plain_run_measures_the_headline_alone():
+    p, lines, _ = _run(["--gpus", "2", "--nest", "cfg4,cfg5"], full=False)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len(lines) == 1
+    line = lines[0]
+    assert line["n_gpus"] == 2 and line["value"] > 0 and line["steps"] == 3 and line["ms_per_step"] > 0
+    assert not {"exchange", "inprocess", "cfg4", "cfg5", "nested_error"} & set(line)
 
 
 def test_a_rank_failing_in_the_exchange_leg_costs_only_that_leg():
