@@ -16,7 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "fedagg.hip")
 # every translation unit of libfedagg.so: compiled to objects separately (an
 # unchanged unit is not recompiled), then linked
-SRCS = [SRC, os.path.join(HERE, "csrc", "robust.hip"), os.path.join(HERE, "csrc", "median.hip")]
+SRCS = [SRC, os.path.join(HERE, "csrc", "robust.hip"), os.path.join(HERE, "csrc", "median.hip"),
+        os.path.join(HERE, "csrc", "trimmed.hip")]
+# headers under csrc/ that the units share: a change rebuilds every unit
+CSRC_HEADERS = [os.path.join(HERE, "csrc", "sortnet.h")]
 OUT_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(OUT_DIR, "obj")
 OUT = os.path.join(OUT_DIR, "libfedagg.so")
@@ -61,7 +64,7 @@ def _stale(target: str, deps) -> bool:
 
 
 def needs_rebuild() -> bool:
-    return _stale(OUT, SRCS + [HEADER, __file__])
+    return _stale(OUT, SRCS + CSRC_HEADERS + [HEADER, __file__])
 
 
 def build_walker(force: bool = False, verbose: bool = False) -> str:
@@ -97,7 +100,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # the translation units compile side by side (one hipcc each)
     jobs = []
     for src, obj in zip(SRCS, objs):
-        if force or _stale(obj, [src, HEADER, __file__]):
+        if force or _stale(obj, [src, HEADER, __file__, *CSRC_HEADERS]):
             tmp = obj + ".tmp.o"
             cmd = [hipcc(), *HIPCC_FLAGS, "-c", "-o", tmp, src]
             if verbose:

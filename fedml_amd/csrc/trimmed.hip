@@ -1,0 +1,236 @@
+// trimmed.hip — gfx950 kernel of the coordinate-wise trimmed mean (Yin et
+// al.: every coordinate drops its `trim` smallest and `trim` largest client
+// values and averages the rest), exported through include/fedagg.h
+// (fedagg_trimmed_mean, where the operation is specified) and linked into
+// libfedagg.so.  Its own translation unit: the unpruned networks compile
+// beside median.hip's pruned ones, not after them.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <type_traits>
+
+#include "../../include/fedagg.h"
+#include "sortnet.h"
+
+extern "C" int fedagg_set_error_internal(int code, const char* msg);
+
+namespace {
+
+int set_error(int code, const std::string& msg) { return fedagg_set_error_internal(code, msg.c_str()); }
+
+int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(static_cast<int>(e), std::string(what) + ": " + hipGetErrorString(e));
+  return FEDAGG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The median kernel's form (median.hip: one lane per column, the column's K
+// values in KMAX registers, loads in the SGPR-base + 32-bit-offset form, the
+// slot pointers of a padded tier staged in LDS), with three differences:
+//   - every rank is needed, so the pairwise network runs unpruned (1,471
+//     comparators at 128 slots against ~1,040 kept by the median);
+//   - padding is +inf only, all of it above rank K - 1, so ranks below K are
+//     those of the column itself;
+//   - fminf / fmaxf drop a NaN and duplicate its partner, so no NaN enters
+//     the network: each is counted and replaced by +inf as it arrives.  The
+//     replacements sit with the real +inf at the top; with count <= trim the
+//     kept ranks trim .. K-trim-1 hold exactly the specification's multiset
+//     (NaN ranks above +inf there too), with count > trim the result is NaN.
+// The sum is the specification's sequential fp32 chain over the sorted
+// registers, fully unrolled; which slots count is decided by the
+// wave-uniform predicate trim <= r < K - trim, so no register array is
+// indexed by a runtime value.
+
+// what the chain adds for a sorted selection value, and the final rounding
+template <class E>
+struct TrimVal;
+template <>
+struct TrimVal<MedF32> {
+  static __device__ __forceinline__ float value(float v) { return v; }
+  static __device__ __forceinline__ float round(float f) { return f; }
+};
+template <>
+struct TrimVal<MedBF16> {
+  static __device__ __forceinline__ float value(float v) { return v; }  // bf16 widened exactly
+  static __device__ __forceinline__ uint16_t round(float f) {
+    const __bf16 b = static_cast<__bf16>(f);  // v_cvt_pk_bf16_f32: RNE
+    return __builtin_bit_cast(uint16_t, b);
+  }
+};
+template <>
+struct TrimVal<MedF16> {
+  // the selection value is an order key: back to the f16 bits, then v_cvt_f32_f16
+  static __device__ __forceinline__ float value(float v) {
+    return static_cast<float>(__builtin_bit_cast(_Float16, MedF16::narrow(v)));
+  }
+  static __device__ __forceinline__ uint16_t round(float f) {
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));  // v_cvt_f16_f32: RNE
+  }
+};
+
+template <class E>
+using raw_bits_t = std::conditional_t<sizeof(typename E::S) == 4, uint32_t, uint16_t>;
+template <class E>
+constexpr typename E::S trim_pos_inf() {
+  return __builtin_bit_cast(typename E::S, static_cast<raw_bits_t<E>>(E::kPosInf));
+}
+
+// +inf in each element type: what a padded slot's load returns
+template <class E>
+__device__ typename E::S g_trimmed_pad = trim_pos_inf<E>();
+
+// Columns [col0, col0 + N) of the rows; out points at column col0's slot.
+// Launches cover at most 2^30 columns (kTrimmedChunk) so that a lane's byte
+// offset from the (wave-uniform) row base + col0 fits in 32 bits.
+template <int KMAX, bool FULL, int BS, class E, bool OFF = false>
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void trimmed_mean_kernel(const typename E::S* const* __restrict__ src, int K,
+                                                          int64_t N, int trim, typename E::S* __restrict__ out,
+                                                          int64_t col0 = 0) {
+  using S = typename E::S;
+  const int64_t e = int64_t(blockIdx.x) * BS + threadIdx.x;
+  if constexpr (FULL) K = KMAX;  // K == KMAX: no padding, no per-client conditions
+  // K < KMAX: the KMAX slot pointers (pads point at a +inf constant) staged
+  // in LDS once per block, as in median_kernel
+  __shared__ const S* tab[FULL ? 1 : KMAX];
+  if constexpr (!FULL) {
+    for (int i = threadIdx.x; i < KMAX; i += BS) tab[i] = i < K ? src[i] : &g_trimmed_pad<E>;
+    __syncthreads();
+  }
+  if (e >= N) return;
+  // the host guarantees N * sizeof(S) < 2^32 per launch
+  const uint32_t boff = uint32_t(e) * uint32_t(sizeof(S));
+  float v[KMAX];
+  int nans = 0;
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) {
+    // at most 16 row pointers live in SGPRs (see median_kernel)
+    if (c % 16 == 0 && c) __builtin_amdgcn_sched_barrier(0);
+    const bool live = FULL || c < K;
+    const S* p;
+    if constexpr (FULL) {
+      p = src[c];
+    } else {
+      // readfirstlane returns int: through uint32_t, or a low word with its
+      // top bit set sign-extends over the high word
+      const uint64_t t = reinterpret_cast<uint64_t>(tab[c]);
+      const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t >> 32))));
+      const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t))));
+      p = reinterpret_cast<const S*>((uint64_t(hi) << 32) | uint64_t(lo));
+    }
+    const char __attribute__((address_space(1)))* row;
+    if constexpr (OFF)
+      row = live ? row_base(p, col0) : reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
+    else
+      row = reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
+    // a padded slot reads the +inf constant: lane offset 0 on the pad's address
+    S x = cols_load(reinterpret_cast<const S __attribute__((address_space(1)))*>(row + (live ? boff : 0u)));
+    if constexpr (sizeof(S) == 2) {
+      // 16-bit rows test the raw value as it widens (holding every raw value
+      // until all loads have landed would double the live registers)
+      const bool n = E::raw_nan(x);
+      nans += n ? 1 : 0;
+      x = n ? trim_pos_inf<E>() : x;
+    }
+    v[c] = E::widen(x);
+  }
+  if constexpr (sizeof(S) == 4) {
+    // fp32 tests after every load is in flight: one unordered compare, a
+    // count and a select per value
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) {
+      const bool n = __builtin_isnan(v[c]);
+      nans += n ? 1 : 0;
+      v[c] = n ? __builtin_huge_valf() : v[c];
+    }
+  }
+  pairwise_sort<KMAX>(v);  // every output slot is live: nothing is pruned
+  // acc = s[trim], then acc = fl32(acc + s[r]) for r = trim+1 .. K-trim-1,
+  // as one uniform chain from -0: a slot outside the kept ranks adds -0,
+  // and y + (-0) = y for every y (-0 and NaN included), so the first kept
+  // value enters as itself and nothing else moves the sum.  One
+  // wave-uniform predicate per slot, trim <= r < K - trim as a single
+  // unsigned compare.  The predicates are made after the sort, 16 slots at a
+  // time: computed up front, their 128 lane masks spilled out of the SGPRs.
+  const uint32_t kept = uint32_t(K - 2 * trim);
+  float acc = -0.f;
+#pragma unroll
+  for (int r = 0; r < KMAX; ++r) {
+    if (r % 16 == 0) __builtin_amdgcn_sched_barrier(0);
+    const float x = TrimVal<E>::value(v[r]);
+    acc = acc + (uint32_t(r - trim) < kept ? x : -0.f);
+  }
+  const float mean = acc / float(kept);  // IEEE division (the build's correctly rounded divide)
+  out[e] = TrimVal<E>::round(nans > trim ? __builtin_nanf("") : mean);
+}
+
+constexpr int64_t kTrimmedChunk = int64_t(1) << 30;  // columns per launch of the 32-bit-offset kernel
+
+template <int KMAX, class E>
+int launch_trimmed(const typename E::S* const* src, int K, int64_t N, int trim, typename E::S* out, hipStream_t st) {
+  constexpr int BS = 64;  // the median kernel's block (median.hip launch_median)
+  for (int64_t c0 = 0; c0 < N; c0 += kTrimmedChunk) {
+    const int64_t n = N - c0 < kTrimmedChunk ? N - c0 : kTrimmedChunk;
+    const int64_t grid = (n + BS - 1) / BS;
+    if (K == KMAX && c0 == 0)
+      hipLaunchKernelGGL((trimmed_mean_kernel<KMAX, true, BS, E>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
+                         trim, out, c0);
+    else if (c0 == 0)
+      hipLaunchKernelGGL((trimmed_mean_kernel<KMAX, false, BS, E>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
+                         trim, out, c0);
+    else  // past 2^30 columns: the padded kernel (correct for K == KMAX too) with the row offset
+      hipLaunchKernelGGL((trimmed_mean_kernel<KMAX, false, BS, E, true>), dim3(unsigned(grid)), dim3(BS), 0, st, src,
+                         K, n, trim, out + c0, c0);
+  }
+  return check_launch("fedagg_trimmed_mean");
+}
+
+template <class E>
+int trimmed_dispatch(const typename E::S* const* d_src, int32_t K, int64_t N, int32_t trim, typename E::S* d_out,
+                     hipStream_t st) {
+  if (K <= 8) return launch_trimmed<8, E>(d_src, K, N, trim, d_out, st);
+  if (K <= 16) return launch_trimmed<16, E>(d_src, K, N, trim, d_out, st);
+  if (K <= 24) return launch_trimmed<24, E>(d_src, K, N, trim, d_out, st);
+  if (K <= 32) return launch_trimmed<32, E>(d_src, K, N, trim, d_out, st);
+  if (K <= 48) return launch_trimmed<48, E>(d_src, K, N, trim, d_out, st);
+  if (K <= 64) return launch_trimmed<64, E>(d_src, K, N, trim, d_out, st);
+  if (K <= 96) return launch_trimmed<96, E>(d_src, K, N, trim, d_out, st);
+  return launch_trimmed<128, E>(d_src, K, N, trim, d_out, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fedagg_trimmed_mean(int32_t dtype, const void* const* d_src, int32_t K, int64_t N, int32_t trim, void* d_out,
+                        uint32_t flags, fedagg_stream_t stream) {
+  (void)flags;  // one kernel form for every alignment
+  if (K < 1 || N < 0) return set_error(FEDAGG_EINVAL, "fedagg_trimmed_mean: K must be >= 1 and N >= 0");
+  if (trim < 0 || 2 * int64_t(trim) >= int64_t(K))
+    return set_error(FEDAGG_EINVAL, "fedagg_trimmed_mean: trim must be >= 0 and leave K - 2 * trim >= 1 values");
+  if (!d_src || !d_out) return set_error(FEDAGG_EINVAL, "fedagg_trimmed_mean: null pointer");
+  if (dtype != FEDAGG_DT_F32 && dtype != FEDAGG_DT_BF16 && dtype != FEDAGG_DT_F16)
+    return set_error(FEDAGG_EINVAL, "fedagg_trimmed_mean: dtype must be FEDAGG_DT_F32, _BF16 or _F16");
+  if (K > FEDAGG_TRIMMED_MAX_CLIENTS)
+    return set_error(FEDAGG_ENOKERNEL, "fedagg_trimmed_mean: the kernel holds at most " +
+                                           std::to_string(FEDAGG_TRIMMED_MAX_CLIENTS) + " clients (K = " +
+                                           std::to_string(K) + ")");
+  if (N == 0) return FEDAGG_OK;
+  auto st = reinterpret_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case FEDAGG_DT_F32:
+      return trimmed_dispatch<MedF32>(reinterpret_cast<const float* const*>(d_src), K, N, trim,
+                                      static_cast<float*>(d_out), st);
+    case FEDAGG_DT_BF16:
+      return trimmed_dispatch<MedBF16>(reinterpret_cast<const uint16_t* const*>(d_src), K, N, trim,
+                                       static_cast<uint16_t*>(d_out), st);
+    default:
+      return trimmed_dispatch<MedF16>(reinterpret_cast<const uint16_t* const*>(d_src), K, N, trim,
+                                      static_cast<uint16_t*>(d_out), st);
+  }
+}
+
+}  // extern "C"

@@ -23,6 +23,19 @@ that are pure reductions over the client axis.
                 sample count (compute_a_score), int(beta * K) dropped at each
                 end, then ordinary FedAvg (our kernel) on the survivors.
 
+"wise_trimmed_mean"
+                Not in FedML: the coordinate-wise trimmed mean of Yin et al.
+                FedML's "trimmed_mean" trims per client (whole clients, by
+                sample count); "wise_trimmed_mean" trims per coordinate: every
+                element of every key drops its int(beta * K) smallest and
+                largest client values and averages the rest
+                (fedagg_trimmed_mean, specified in include/fedagg.h: one
+                launch per row group up to 128 clients, the same rule in torch
+                ops above that; BatchNorm statistics included, integer keys
+                as fl32(v)).  Up to int(beta * K) clients sending anything,
+                NaN and inf included, cannot move a coordinate outside the
+                range of the honest values.
+
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
                 the K x K squared distances of the clients' weight vectors are
@@ -84,8 +97,9 @@ DEFENSE_SLSGD = "slsgd"
 DEFENSE_CCLIP = "cclip"
 DEFENSE_ROBUST_LEARNING_RATE = "robust_learning_rate"
 DEFENSE_WEAK_DP = "weak_dp"
+DEFENSE_WISE_TRIMMED_MEAN = "wise_trimmed_mean"  # not a FedML defense type: Yin et al.'s per-coordinate rule
 SUPPORTED = (DEFENSE_WISE_MEDIAN, DEFENSE_TRIMMED_MEAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_NORM_DIFF_CLIPPING,
-             DEFENSE_SLSGD, DEFENSE_CCLIP, DEFENSE_ROBUST_LEARNING_RATE, DEFENSE_WEAK_DP)
+             DEFENSE_SLSGD, DEFENSE_CCLIP, DEFENSE_ROBUST_LEARNING_RATE, DEFENSE_WEAK_DP, DEFENSE_WISE_TRIMMED_MEAN)
 # FedMLDefender constructs these but lists them under none of its
 # before / on / after-aggregation hooks (fedml_defender.py:131-154), so the
 # plugin path aggregates as if no defense were set; they act only through
@@ -212,6 +226,138 @@ def trimmed_mean_before_aggregation(raw_client_grad_list: Sequence, beta: float)
     if beta > 1 / 2 or beta < 0:
         raise ValueError("the bound of beta is [0, 1/2)")
     return trimmed_mean(raw_client_grad_list, int(beta * len(raw_client_grad_list)))
+
+
+# ---- coordinate-wise trimmed mean (csrc/trimmed.hip) ---------------------------
+
+TRIMMED_MAX_CLIENTS = nat.TRIMMED_MAX_CLIENTS  # fedagg_trimmed_mean holds up to 128 clients
+
+
+def trimmed_mean_rows(d_ptrs: torch.Tensor, K: int, N: int, trim: int, out: torch.Tensor,
+                      aligned: bool = False) -> None:
+    """Coordinate-wise trimmed mean of K device rows of out's dtype (fp32, bf16
+    or f16; fedagg_trimmed_mean, specified in include/fedagg.h): per column
+    the `trim` smallest and `trim` largest values dropped, the rest summed in
+    fp32 in ascending order and divided by their number.  K <= 128.  aligned
+    is accepted for symmetry with median_rows; the kernel has one form."""
+    kn._require_cuda(out, "trimmed_mean")
+    if out.dtype not in _MEDIAN_DT:
+        raise TypeError(f"trimmed_mean: fp32, bf16 or f16 rows (got {out.dtype})")
+    flags = nat.FEDAGG_ALIGNED16 if aligned and out.data_ptr() % 16 == 0 else 0
+    nat.check(nat.lib().fedagg_trimmed_mean(_MEDIAN_DT[out.dtype], d_ptrs.data_ptr(), K, N, trim, out.data_ptr(),
+                                            flags, nat.stream_handle()), "trimmed_mean")
+
+
+def _order_keys(x: torch.Tensor) -> torch.Tensor:
+    """int32 keys of fp32 values whose integer order is the kernels' total
+    order (-inf < negatives < -0 < +0 < positives < +inf < every NaN).  The
+    map is its own inverse on non-NaN values; the NaN key maps back to a NaN."""
+    b = x.view(torch.int32)
+    k = b ^ ((b >> 31) & 0x7FFFFFFF)
+    return torch.where(torch.isnan(x), torch.full_like(k, 0x7FFFFFFF), k)
+
+
+def trimmed_mean_rows_torch(rows, trim: int, chunk_cols: "int | None" = None) -> torch.Tensor:
+    """The specification of fedagg_trimmed_mean in torch ops, on any device
+    and for any K: the slow path above 128 clients.  rows: a (K, N) tensor or
+    a list of K rows of N elements (fp32, bf16 or f16).  Per column chunk the
+    order keys are sorted, mapped back to values and added in ascending rank
+    order, one fp32 add per kept rank, then divided by their count (a tensor
+    divisor: torch turns a division by a Python scalar into a multiplication
+    by its reciprocal on the GPU).  chunk_cols: columns per chunk (default:
+    temporaries of about 1 GiB)."""
+    K = len(rows)
+    if K < 1:
+        raise ValueError("trimmed mean of no rows")
+    if trim < 0 or K - 2 * trim < 1:
+        raise ValueError(f"trim = {trim} leaves no value of K = {K}")
+    r0 = rows[0]
+    if r0.dtype not in _MEDIAN_DT:
+        raise TypeError(f"trimmed_mean: fp32, bf16 or f16 rows (got {r0.dtype})")
+    N = r0.numel()
+    if chunk_cols is None:
+        chunk_cols = max(1, (1 << 30) // (32 * K))  # widened values, keys, sorted keys and sort indices
+    out = torch.empty(N, dtype=r0.dtype, device=r0.device)
+    count = torch.full((1,), float(K - 2 * trim), dtype=torch.float32, device=r0.device)
+    for c0 in range(0, N, chunk_cols):
+        c1 = min(N, c0 + chunk_cols)
+        x = rows[:, c0:c1] if isinstance(rows, torch.Tensor) else torch.stack([r[c0:c1] for r in rows])
+        keys = torch.sort(_order_keys(x.float().contiguous()), dim=0).values
+        s = (keys ^ ((keys >> 31) & 0x7FFFFFFF)).view(torch.float32)
+        acc = s[trim].clone()  # the chain starts from the value, not from 0.0
+        for r in range(trim + 1, K - trim):
+            acc += s[r]
+        out[c0:c1] = (acc / count).to(r0.dtype)  # one rounding to the row dtype, nearest-even
+    return out
+
+
+def trimmed_row_dtype(dts) -> "torch.dtype | None":
+    """The dtype of the float keys' rows for keys of dtypes `dts`, by
+    median_row_dtype's rule: fp32 when any key is fp32 or two float widths
+    meet (the 16-bit keys widen exactly), else the model's own bf16 / f16;
+    None for a model of integer keys only.  Integer / bool keys sit in an fp32
+    row as fl32(v) whatever the floats are."""
+    dts = set(dts)
+    floats = dts & {torch.float32, torch.bfloat16, torch.float16}
+    if not dts - floats <= {torch.int64, torch.int32, torch.bool}:
+        raise NotImplementedError("wise_trimmed_mean on the GPU takes fp32, bf16 and f16 keys and int64 / int32 / "
+                                  f"bool buffers (got {sorted(map(str, dts))})")
+    if not floats:
+        return None
+    return torch.float32 if torch.float32 in floats or len(floats) > 1 else next(iter(floats))
+
+
+def coordinate_wise_trimmed_mean(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], beta: float, device=None
+                                 ) -> "OrderedDict":
+    """The coordinate-wise trimmed mean of Yin et al. over the clients' dicts:
+    every coordinate of EVERY key (BatchNorm statistics and counters too)
+    drops its int(beta * K) smallest and largest client values and averages
+    the rest (fedagg_trimmed_mean; trimmed_mean_rows_torch above 128
+    clients).  Sample counts are ignored, as by the median.  Returns a new
+    OrderedDict in client 0's key order, on the inputs' device; integer keys
+    come back fp32, as FedMLAggOperator.agg returns them.  No client dict is
+    modified."""
+    if beta < 0 or beta >= 1 / 2:
+        raise ValueError("the bound of beta is [0, 1/2)")
+    K = len(raw_client_grad_list)
+    trim = int(beta * K)
+    if K - 2 * trim < 1:
+        raise ValueError(f"beta = {beta} trims every one of {K} clients")
+    dicts = [raw_client_grad_list[i][1] for i in range(K)]
+    keys = list(dicts[0].keys())
+    for d in dicts[1:]:
+        for k in keys:
+            d[k]  # KeyError for a missing key
+    if not keys:
+        return OrderedDict()
+    _one_device(dicts[0], keys, "wise_trimmed_mean")
+    t0 = dicts[0][keys[0]]
+    dev = t0.device if t0.is_cuda else (torch.device(device) if device is not None else
+                                        torch.device("cuda", torch.cuda.current_device()))
+    floats = {torch.float32, torch.bfloat16, torch.float16}
+    row_dt = trimmed_row_dtype(dicts[0][k].dtype for k in keys)
+    result = {}
+    with torch.cuda.device(dev):
+        # 16-bit keys of a promoted model are declared fp32: put() widens them
+        layout = [(k, tuple(dicts[0][k].shape), row_dt if dicts[0][k].dtype in floats else dicts[0][k].dtype)
+                  for k in keys]
+        bucket = ClientBucket(layout, K, dev)
+        for i in range(K):
+            bucket.put(i, {k: dicts[i][k] for k in keys}, 1)
+        bucket.sync_ingest()
+        for g in bucket.groups.values():  # the float keys' row; integer keys in an fp32 row
+            if K <= TRIMMED_MAX_CLIENTS:
+                row = torch.empty(g.padded, dtype=g.dtype, device=dev)
+                trimmed_mean_rows(g.d_ptrs, K, g.length, trim, row, aligned=True)
+            else:
+                row = trimmed_mean_rows_torch(g.rows[:, :g.length], trim)
+            if not t0.is_cuda:
+                row = row.cpu()
+            for k, o, n, shp in zip(g.keys, g.offsets, g.numels, g.shapes):
+                result[k] = row[o:o + n].view(shp)
+        if t0.is_cuda:
+            torch.cuda.current_stream().synchronize()  # the staging bucket goes out of scope
+    return OrderedDict((k, result[k]) for k in keys)
 
 
 # ---- distance-based defenses (csrc/robust.hip) ---------------------------------

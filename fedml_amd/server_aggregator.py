@@ -10,7 +10,8 @@ implementation of the reference's operator.  Several of FedML's defenses are
 reductions over the client axis and run on the GPU too (fedml_amd.defense):
 ``defense_type`` "wise_median" (on aggregation) and "trimmed_mean" (before
 aggregation), dispatched exactly as FedMLDefender does
-(core/security/fedml_defender.py:131-171); so do the distance-based
+(core/security/fedml_defender.py:131-171), and "wise_trimmed_mean", the
+per-coordinate trimmed mean FedML lacks (on aggregation); so do the distance-based
 "krum" / "multikrum", "norm_diff_clipping", "slsgd" and "cclip".  "robust_learning_rate" and
 "weak_dp" are accepted and, as in FedML, leave the plugin path a plain FedAvg
 (FedMLDefender lists them under none of the three hooks; the GPU version of the
@@ -49,6 +50,7 @@ _DEFENSE_ATTRS = {
     dfn.DEFENSE_NORM_DIFF_CLIPPING: ("norm_bound",),
     dfn.DEFENSE_CCLIP: ("bucket_size",),
     dfn.DEFENSE_SLSGD: ("trim_param_b",),  # then the alpha check, then option_type
+    dfn.DEFENSE_WISE_TRIMMED_MEAN: ("beta",),  # ours, not FedML's: the per-coordinate trimmed mean
 }
 
 
@@ -138,6 +140,10 @@ class ServerAggregator(ABC):
         (fedml_defender.py:163-174), otherwise FedMLAggOperator.agg."""
         if _defense(self.args) == dfn.DEFENSE_WISE_MEDIAN:
             return dfn.coordinate_wise_median(raw_client_model_or_grad_list, getattr(self.args, "fedagg_device", None))
+        if _defense(self.args) == dfn.DEFENSE_WISE_TRIMMED_MEAN:
+            # not a FedML defense: the per-coordinate trimmed mean replaces the operator as the median does
+            return dfn.coordinate_wise_trimmed_mean(raw_client_model_or_grad_list, self.args.beta,
+                                                    getattr(self.args, "fedagg_device", None))
         if _defense(self.args) == dfn.DEFENSE_SLSGD:
             # defend_on_aggregation (slsgd_defense.py:54-67): the base operator, then the
             # moving average with the global model (extra_auxiliary_info, :81-85)

@@ -351,6 +351,34 @@ int fedagg_median(int32_t dtype, const void* const* d_src, int32_t K,
                   int64_t N, void* d_out, uint32_t flags,
                   fedagg_stream_t stream);
 
+/* Coordinate-wise trimmed mean (Yin et al.; the "wise_trimmed_mean" defense)
+ * over K rows of dtype FEDAGG_DT_F32, _BF16 or _F16 (d_src and d_out of that
+ * dtype), 0 <= trim, K - 2 * trim >= 1.  Every column independently:
+ *   1. its K values are ordered by the IEEE total order of the median
+ *      kernels, -inf < negatives < -0 < +0 < positives < +inf, every NaN (either
+ *      sign, any payload) above +inf; tied values are bit-identical;
+ *   2. with s[0 .. K-1] the column in that order, the kept values are
+ *      s[trim .. K-trim-1], M = K - 2 * trim of them;
+ *   3. they are summed in fp32 in ascending rank order as one sequential
+ *      chain: acc = s[trim] (the value, not 0.0: an all -0 column stays -0),
+ *      then acc = fl32(acc + s[r]) for r = trim+1 .. K-trim-1; 16-bit values
+ *      are widened exactly first;
+ *   4. out = fl32(acc / fl32(M)), an IEEE-rounded fp32 division, for 16-bit
+ *      rows then rounded once to the row dtype, round-to-nearest-even;
+ *   5. a column holding more than trim NaNs gives a NaN (unspecified
+ *      payload); trim NaNs or fewer are all trimmed.  A kept +inf with a kept
+ *      -inf gives the arithmetic's NaN.  Up to trim clients sending NaN or
+ *      +-inf cannot break a coordinate.
+ * One lane per column holds the column in registers and sorts it with an
+ * unpruned pairwise network (K tiers 8 .. 128, launches of 2^30 columns), for
+ * every alignment; flags is reserved.  FEDAGG_EINVAL for K < 1, N < 0,
+ * trim < 0, 2 * trim >= K, a null pointer or another dtype; FEDAGG_ENOKERNEL
+ * for K > FEDAGG_TRIMMED_MAX_CLIENTS (callers sort in torch ops above it). */
+#define FEDAGG_TRIMMED_MAX_CLIENTS 128
+int fedagg_trimmed_mean(int32_t dtype, const void* const* d_src, int32_t K,
+                        int64_t N, int32_t trim, void* d_out, uint32_t flags,
+                        fedagg_stream_t stream);
+
 /* Distance-based defenses (csrc/robust.hip).  Rows are K fp32 device
  * pointers; the columns that count (FedML's vectorize_weight: every key but
  * BatchNorm running stats and counters, core/security/common/utils.py:8-21)
