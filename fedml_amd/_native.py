@@ -25,8 +25,9 @@ FEDAGG_ACC_FP32 = 1
 
 DT_F32, DT_BF16, DT_F16, DT_F64, DT_I64, DT_I32 = 0, 1, 2, 3, 4, 5
 DIST_CHUNK, PAIR_CHUNK = 1024, 256  # FEDAGG_DIST_CHUNK / FEDAGG_PAIR_CHUNK
-WORK_DIST2, WORK_PAIRDIST2, WORK_PAIRGRAM = 0, 1, 2
+WORK_DIST2, WORK_PAIRDIST2, WORK_PAIRGRAM, WORK_WSUM_DIST2 = 0, 1, 2, 3
 TRIMMED_MAX_CLIENTS = 128  # FEDAGG_TRIMMED_MAX_CLIENTS
+GEOMED_MAX_CLIENTS = 128  # FEDAGG_GEOMED_MAX_CLIENTS
 # FEDAGG_FEDOPT_*: the launch kinds of fedagg_wsum_fedopt_batch (besides the FEDAGG_OPT_* codes)
 FEDOPT_AVG, FEDOPT_SGD, FEDOPT_ADAM, FEDOPT_ADAMW, FEDOPT_ADAGRAD, FEDOPT_RMSPROP = 0, 16, 17, 18, 19, 20
 
@@ -89,6 +90,7 @@ SIGNATURES = {
     "fedagg_device_round_f32": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     "fedagg_robust_work_len": (_I64, [_I32, _I32, _I64]),
     "fedagg_dist2_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
+    "fedagg_wsum_dist2_f32": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _U32, _P]),
     "fedagg_pairdist2_f32": (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_pairgram2_f32": (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_clip_diff_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),

@@ -37,6 +37,7 @@
 
 
 extern "C" int fedagg_set_error_internal(int code, const char* msg);
+extern "C" int64_t fedagg_wsum_dist2_work_len_internal(int32_t K, int64_t n_chunks);
 
 namespace {
 
@@ -1166,6 +1167,7 @@ int64_t fedagg_robust_work_len(int32_t kind, int32_t K, int64_t n_chunks) {
     const int NT = pair_tiles(K);
     return int64_t(NT) * grid_groups(NT, n_chunks, 0, 0) * (kPT * kPT);
   }
+  if (kind == FEDAGG_WORK_WSUM_DIST2) return fedagg_wsum_dist2_work_len_internal(K, n_chunks);  // geomed.hip
   return -1;
 }
 

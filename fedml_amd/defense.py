@@ -36,6 +36,17 @@ that are pure reductions over the client axis.
                 NaN and inf included, cannot move a coordinate outside the
                 range of the honest values.
 
+"geomed"        Not in FedML under this name: the geometric median of the clients'
+                whole updates (RFA, Pillutla et al.; breakdown point 1/2 over
+                clients, not per coordinate) by the smoothed Weiszfeld
+                iteration, specified at geometric_median_loop.  One iteration
+                is one pass over the rows: the weighted sum z and every
+                client's distance to it (fedagg_wsum_dist2_f32, up to 128
+                clients; fedagg_wsum_f32 + fedagg_dist2_f32 above that and
+                where "auto" measured the pair faster).  FedML's own
+                "geometric_median" / "RFA" loop (a Python set of weights, a
+                truncating zip) is NOT reproduced: those names stay refused.
+
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
                 the K x K squared distances of the clients' weight vectors are
@@ -77,6 +88,7 @@ and a clipped client's divisor can differ in its last bit.
 """
 from __future__ import annotations
 
+import logging
 import math
 from collections import OrderedDict
 from typing import List, Sequence, Tuple
@@ -98,8 +110,10 @@ DEFENSE_CCLIP = "cclip"
 DEFENSE_ROBUST_LEARNING_RATE = "robust_learning_rate"
 DEFENSE_WEAK_DP = "weak_dp"
 DEFENSE_WISE_TRIMMED_MEAN = "wise_trimmed_mean"  # not a FedML defense type: Yin et al.'s per-coordinate rule
+DEFENSE_GEOMED = "geomed"  # not a FedML defense type either: our geometric median (RFA), see geometric_median
 SUPPORTED = (DEFENSE_WISE_MEDIAN, DEFENSE_TRIMMED_MEAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_NORM_DIFF_CLIPPING,
-             DEFENSE_SLSGD, DEFENSE_CCLIP, DEFENSE_ROBUST_LEARNING_RATE, DEFENSE_WEAK_DP, DEFENSE_WISE_TRIMMED_MEAN)
+             DEFENSE_SLSGD, DEFENSE_CCLIP, DEFENSE_ROBUST_LEARNING_RATE, DEFENSE_WEAK_DP, DEFENSE_WISE_TRIMMED_MEAN,
+             DEFENSE_GEOMED)
 # FedMLDefender constructs these but lists them under none of its
 # before / on / after-aggregation hooks (fedml_defender.py:131-154), so the
 # plugin path aggregates as if no defense were set; they act only through
@@ -782,3 +796,298 @@ class RobustLearningRateDefense:
 
     def get_malicious_client_idxs(self):
         return []
+
+
+# ---- geometric median (csrc/geomed.hip) ----------------------------------------
+
+GEOMED_MAX_CLIENTS = nat.GEOMED_MAX_CLIENTS  # fedagg_wsum_dist2_f32 holds up to 128 clients
+# a client whose squared norm over the weight columns exceeds this (or is not
+# finite) is dropped by the screen: what is left has every |value| <= 2^126, so
+# every |z| <= 2^126 and no fp32 difference x - z can overflow
+GEOMED_MAX_NORM2 = 2.0 ** 252
+# "auto": the K tiers of the fused kernel (K <= tier) where its median time
+# beat the unfused pair's by more than the larger min-max spread of the two
+# (tools/geomed_probe.py -> profiles/geomed_probe.json, NOTES.md §7b); a tier
+# that did not win would take the unfused pair.  Measured at 25,610,152
+# columns: 1.79x to 1.92x at every tier, spreads under 0.05 ms
+GEOMED_AUTO_FUSED = {8: True, 16: True, 32: True, 64: True, 128: True}
+
+
+def geomed_auto_fused(K: int) -> bool:
+    """Whether "auto" runs the fused kernel for K clients (GEOMED_AUTO_FUSED)."""
+    if K > GEOMED_MAX_CLIENTS:
+        return False
+    return GEOMED_AUTO_FUSED[min(t for t in GEOMED_AUTO_FUSED if K <= t)]
+
+
+class NonFiniteDistance(ArithmeticError):
+    """A Weiszfeld pass returned a non-finite squared distance."""
+
+    def __init__(self, iteration: int, D):
+        super().__init__(f"non-finite squared distance in Weiszfeld pass {iteration}")
+        self.iteration = iteration
+        self.D = D
+
+
+class GeomedInfo:
+    """What geometric_median did: `iterations` weight updates (iterations + 1
+    passes), the `objective` f_0 .. f_T, the final float64 `weights` (0 for a
+    dropped client), the indices of the clients `dropped` by the screen and
+    the `method` the passes ran with."""
+
+    def __init__(self, iterations: int, objective: list, weights=None, dropped=(), method: str = ""):
+        self.iterations = iterations
+        self.objective = objective
+        self.weights = weights
+        self.dropped = list(dropped)
+        self.method = method
+
+    def __repr__(self):
+        return (f"GeomedInfo(iterations={self.iterations}, objective={self.objective}, dropped={self.dropped}, "
+                f"method={self.method!r})")
+
+
+def wsum_dist2_rows(d_ptrs: torch.Tensor, d_w, K: int, chunks: torch.Tensor, n_chunks: int, z: torch.Tensor,
+                    device) -> torch.Tensor:
+    """One fused Weiszfeld pass (fedagg_wsum_dist2_f32): the weighted sum of
+    the K fp32 device rows into z's chunked columns and, returned, the K fp64
+    squared distances of the rows to it over those columns.  d_w: K device
+    floats or kernels.HostWeights.  K <= GEOMED_MAX_CLIENTS."""
+    kn._require_cuda(z, "wsum_dist2")
+    if z.dtype != torch.float32:
+        raise TypeError("wsum_dist2: fp32 rows and output")
+    out = torch.empty(K, dtype=torch.float64, device=device)
+    work = _work(nat.WORK_WSUM_DIST2, K, n_chunks, device)
+    flags = nat.FEDAGG_ALIGNED16 if z.data_ptr() % 16 == 0 else 0  # the kernel has one form for every alignment
+    if isinstance(d_w, kn.HostWeights):
+        flags |= nat.FEDAGG_HOST_WEIGHTS
+    nat.check(nat.lib().fedagg_wsum_dist2_f32(d_ptrs.data_ptr(), d_w.data_ptr(), K, chunks.data_ptr(), n_chunks,
+                                              z.data_ptr(), out.data_ptr(), work.data_ptr(), work.numel(), flags,
+                                              nat.stream_handle()), "wsum_dist2")
+    return out
+
+
+def weiszfeld_step_unfused(d_ptrs: torch.Tensor, d_w, K: int, N: int, chunks: torch.Tensor, n_chunks: int,
+                           z: torch.Tensor, device, aligned: bool = False) -> torch.Tensor:
+    """The same pass from the two kernels that were there before: fedagg_wsum_f32
+    over the first N columns of the rows into z, then fedagg_dist2_f32 with
+    ref = z over the chunked columns (two reads of the rows).  The path above
+    GEOMED_MAX_CLIENTS clients, and what the fused kernel is checked and timed
+    against.  aligned: the rows are 16-byte aligned (bucket rows are)."""
+    kn.wsum_ptrs(torch.float32, d_ptrs, d_w, K, N, z, aligned)
+    return dist2_rows(d_ptrs, K, z, chunks, n_chunks, device)
+
+
+def weiszfeld_step_torch(rows, w32, cols=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The specification of one Weiszfeld pass in torch ops, on any device.
+    rows: a (K, N) fp32 tensor or a list of K rows; w32: K weights (rounded to
+    fp32 here); cols: index tensor of the columns that count (None: all).
+    Returns (z, D): z[e] = the chain fl(x_0 w_0), fl(acc + fl(x_i w_i)) client
+    by client in fp32 for EVERY column, D[i] = the fp64 sum over cols of the
+    exact squares of the fp32 differences x_i - z."""
+    K = len(rows)
+    if K < 1:
+        raise ValueError("Weiszfeld step over no rows")
+    dev = rows[0].device
+    w = torch.tensor([float(v) for v in w32], dtype=torch.float64).to(torch.float32).to(dev)
+    z = rows[0] * w[0]
+    for i in range(1, K):
+        z = z + rows[i] * w[i]  # two roundings: torch's eager mul, then add
+    zc = z if cols is None else z[cols]
+    D = torch.empty(K, dtype=torch.float64, device=dev)
+    for i in range(K):
+        d = ((rows[i] if cols is None else rows[i][cols]) - zc).double()
+        D[i] = (d * d).sum()
+    return z, D
+
+
+def geomed_weights(D, a, nu: float) -> np.ndarray:
+    """The Weiszfeld weights in float64: d_i = sqrt(D_i), b_i = a_i /
+    max(nu, d_i), w_i = b_i / sum(b), the sum taken left to right."""
+    d = np.sqrt(np.asarray(D, dtype=np.float64))
+    b = [float(ai) / max(float(nu), float(di)) for ai, di in zip(a, d)]
+    total = 0.0
+    for x in b:
+        total += x
+    return np.array([x / total for x in b], dtype=np.float64)
+
+
+def geometric_median_loop(step, a, nu: float = 1e-6, maxiter: int = 16, ftol: float = 1e-6):
+    """Smoothed Weiszfeld iteration (Pillutla et al., RFA), independent of
+    where a pass runs.  step(w32) -> (z, D): the weighted sum of the clients
+    with the K Python floats w32 (already fp32 values) and the K squared
+    distances to it (array-like, float64).  a: the clients' sample weights
+    n_i / sum(n).
+
+        w = a
+        for t = 0, 1, ...:
+            z_t, D = step(fl32(w))
+            f_t = sum_i a_i sqrt(D_i)            (float64, left to right)
+            stop if t == maxiter or (t >= 1 and |f_{t-1} - f_t| <= ftol f_t)
+            w = geomed_weights(D, a, nu)
+
+    so maxiter updates cost maxiter + 1 passes and maxiter = 0 is FedAvg.
+    Returns (z_T, w_T, GeomedInfo): the last pass's sum, the float64 weights
+    it was formed with, and iterations = T with the objectives f_0 .. f_T.
+    Raises NonFiniteDistance when a pass returns a non-finite D."""
+    if maxiter < 0:
+        raise ValueError("maxiter must be >= 0")
+    a = [float(x) for x in a]
+    w = np.array(a, dtype=np.float64)
+    objective = []
+    t = 0
+    while True:
+        z, D = step([float(np.float32(x)) for x in w])
+        D = np.asarray(D, dtype=np.float64)
+        if not np.all(np.isfinite(D)):
+            raise NonFiniteDistance(t, D)
+        f = 0.0
+        for ai, di in zip(a, np.sqrt(D)):
+            f += ai * float(di)
+        objective.append(f)
+        if t == maxiter or (t >= 1 and abs(objective[-2] - f) <= ftol * f):
+            return z, w, GeomedInfo(t, objective, w)
+        w = geomed_weights(D, a, nu)
+        t += 1
+
+
+def geometric_median_screened(make_step, norms2, a, nu: float = 1e-6, maxiter: int = 16, ftol: float = 1e-6):
+    """geometric_median_loop with the lazy screen for non-finite clients.
+    make_step(alive) -> the step over the clients `alive` (indices into a);
+    norms2() -> the K clients' squared norms over the columns that count.
+    Honest rounds run the loop once and pay nothing.  If pass 0 returns a
+    non-finite D, every client whose squared norm is non-finite or above
+    GEOMED_MAX_NORM2 is dropped (a warning names them), a is renormalised over
+    the rest and the loop restarts; ValueError if the dropped clients hold half
+    or more of the sample weight (the breakdown point), RuntimeError if D is
+    non-finite after that.  Returns (z, w, info, alive): w has K entries (0 for
+    a dropped client), info.dropped lists the dropped indices."""
+    K = len(a)
+    a = [float(x) for x in a]
+    alive = list(range(K))
+    try:
+        z, w, info = geometric_median_loop(make_step(alive), a, nu, maxiter, ftol)
+        return z, w, info, alive
+    except NonFiniteDistance as e:
+        if e.iteration != 0:
+            raise RuntimeError(f"geomed: {e} although pass 0 was finite") from e
+    n2 = np.asarray(norms2(), dtype=np.float64)
+    dropped = [i for i in range(K) if not np.isfinite(n2[i]) or n2[i] > GEOMED_MAX_NORM2]
+    if not dropped:
+        raise RuntimeError("geomed: non-finite distances, yet every client's norm is finite and below 2^126")
+    alive = [i for i in range(K) if i not in set(dropped)]
+    lost = 0.0
+    for i in dropped:
+        lost += a[i]
+    kept = 0.0
+    for i in alive:
+        kept += a[i]
+    if lost >= kept:
+        raise ValueError(f"geomed: clients {dropped} sent non-finite or overflowing updates and hold "
+                         f"{lost:.3f} of the sample weight: half or more, the geometric median's breakdown point")
+    logging.warning("geomed: dropped clients %s (non-finite or overflowing updates, %.3f of the sample weight)",
+                    dropped, lost)
+    a2 = [a[i] / kept for i in alive]
+    try:
+        z, w2, info = geometric_median_loop(make_step(alive), a2, nu, maxiter, ftol)
+    except NonFiniteDistance as e:
+        raise RuntimeError(f"geomed: {e} after the non-finite clients {dropped} were dropped") from e
+    w = np.zeros(K, dtype=np.float64)
+    w[alive] = w2
+    info.weights = w
+    info.dropped = dropped
+    return z, w, info, alive
+
+
+def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu: float = 1e-6, maxiter: int = 16,
+                     ftol: float = 1e-6, device=None, method: str = "auto", return_info: bool = False):
+    """The geometric median of the clients' updates (RFA, Pillutla et al.; the
+    "geomed" defense, ours: FedML's own "geometric_median" / "RFA" loop is not
+    reproduced): the point minimising sum_i a_i |x_i - z| over the weight keys,
+    a_i = n_i / sum(n), by geometric_median_loop.  Each pass is one
+    fedagg_wsum_dist2_f32 launch ("fused", up to 128 clients) or fedagg_wsum_f32
+    + fedagg_dist2_f32 ("unfused"); "auto" takes the fused kernel where it was
+    measured faster (GEOMED_AUTO_FUSED) and the pair elsewhere and above 128
+    clients.  One K-double device-to-host copy per pass, as Krum's.
+
+    fp32 models (integer buffers allowed, entering as fl32(v)).  Distances run
+    over the weight keys; the result's weight keys are the last pass's z, and
+    BatchNorm statistics and counters are the weighted sum with the same final
+    weights (one more fedagg_wsum_f32 over the row after a fused run, whose
+    weight columns are bit-identical to z).  Non-finite clients are screened
+    lazily (geometric_median_screened); a NaN in a non-weight key is not
+    looked at and passes through into that key, as in FedAvg.  Returns a new
+    OrderedDict in client 0's key order on the inputs' device (integer keys
+    come back fp32); no client dict is modified.  return_info: also the
+    GeomedInfo."""
+    if method not in ("auto", "fused", "unfused"):
+        raise ValueError(f"geomed method {method!r}: 'auto', 'fused' or 'unfused'")
+    K = len(raw_client_grad_list)
+    if K < 1:
+        raise ValueError("geomed: no clients")
+    dicts = [raw_client_grad_list[i][1] for i in range(K)]
+    keys = list(dicts[0].keys())
+    for d in dicts[1:]:
+        for k in keys:
+            d[k]  # KeyError for a missing key
+    total = 0
+    for n, _ in raw_client_grad_list:
+        total += n
+    a = [n / total for n, _ in raw_client_grad_list]  # ZeroDivisionError at sum(n) = 0, as FedAvg
+    if not keys:
+        return (OrderedDict(), GeomedInfo(0, [], np.array(a), (), method)) if return_info else OrderedDict()
+    if method == "fused" and K > GEOMED_MAX_CLIENTS:
+        raise ValueError(f"the fused Weiszfeld kernel holds at most {GEOMED_MAX_CLIENTS} clients (K = {K})")
+    _one_device(dicts[0], keys, "geomed")
+    on_dev = dicts[0][keys[0]].is_cuda
+    bucket, dev = _float_bucket(dicts[0], K, "geomed", device)
+    fused = method == "fused" or (method == "auto" and geomed_auto_fused(K))
+    with torch.cuda.device(dev):
+        for i, d in enumerate(dicts):
+            _put_float(bucket, i, d, keys)
+        bucket.sync_ingest()
+        g = bucket.groups[torch.float32]
+        chunks, n_chunks = weight_chunks(g, nat.DIST_CHUNK, dev)
+        z = torch.zeros(g.padded, dtype=torch.float32, device=dev)
+        tables = {}
+
+        def table(alive):
+            if len(alive) == K:
+                return g.d_ptrs
+            if tuple(alive) not in tables:
+                tables[tuple(alive)] = kn.upload_i64([g.rows[i].data_ptr() for i in alive], dev)
+            return tables[tuple(alive)]
+
+        def make_step(alive):
+            ptrs, Ka = table(alive), len(alive)
+
+            def step(w32):
+                d_w = kn.weights_for(w32, torch.float32, dev)
+                if fused:
+                    D = wsum_dist2_rows(ptrs, d_w, Ka, chunks, n_chunks, z, dev)
+                else:
+                    D = weiszfeld_step_unfused(ptrs, d_w, Ka, g.length, chunks, n_chunks, z, dev, aligned=True)
+                return z, D.cpu().numpy()
+            return step
+
+        def norms2():
+            return dist2_rows(g.d_ptrs, K, None, chunks, n_chunks, dev).cpu().numpy()
+
+        _, w, info, alive = geometric_median_screened(make_step, norms2, a, nu, maxiter, ftol)
+        info.method = "fused" if fused else "unfused"
+        row = z
+        others = any(n > 0 and not is_weight_param(k) for k, n in zip(g.keys, g.numels))
+        if fused and others:
+            # BatchNorm statistics and counters with the robust weights; the
+            # weight columns come out bit-identical to z
+            row = torch.empty_like(z)
+            w32 = [float(np.float32(w[i])) for i in alive]
+            kn.wsum_ptrs(torch.float32, table(alive), kn.weights_for(w32, torch.float32, dev), len(alive), g.length,
+                         row, True)
+        if not on_dev:
+            row = row.cpu()
+        res = {k: row[o:o + n].view(shp).clone() for k, o, n, shp in zip(g.keys, g.offsets, g.numels, g.shapes)}
+        if on_dev:
+            torch.cuda.current_stream().synchronize()  # the staging bucket goes out of scope
+    out = OrderedDict((k, res[k]) for k in keys)
+    return (out, info) if return_info else out

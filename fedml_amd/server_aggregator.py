@@ -11,7 +11,9 @@ reductions over the client axis and run on the GPU too (fedml_amd.defense):
 ``defense_type`` "wise_median" (on aggregation) and "trimmed_mean" (before
 aggregation), dispatched exactly as FedMLDefender does
 (core/security/fedml_defender.py:131-171), and "wise_trimmed_mean", the
-per-coordinate trimmed mean FedML lacks (on aggregation); so do the distance-based
+per-coordinate trimmed mean FedML lacks, and "geomed", our geometric median
+(RFA; FedML's own "geometric_median" / "RFA" stay refused) (both on
+aggregation); so do the distance-based
 "krum" / "multikrum", "norm_diff_clipping", "slsgd" and "cclip".  "robust_learning_rate" and
 "weak_dp" are accepted and, as in FedML, leave the plugin path a plain FedAvg
 (FedMLDefender lists them under none of the three hooks; the GPU version of the
@@ -144,6 +146,13 @@ class ServerAggregator(ABC):
             # not a FedML defense: the per-coordinate trimmed mean replaces the operator as the median does
             return dfn.coordinate_wise_trimmed_mean(raw_client_model_or_grad_list, self.args.beta,
                                                     getattr(self.args, "fedagg_device", None))
+        if _defense(self.args) == dfn.DEFENSE_GEOMED:
+            # not a FedML defense: our geometric median (RFA) replaces the operator as the median does
+            return dfn.geometric_median(raw_client_model_or_grad_list,
+                                        nu=getattr(self.args, "geomed_nu", 1e-6),
+                                        maxiter=getattr(self.args, "geomed_maxiter", 16),
+                                        ftol=getattr(self.args, "geomed_ftol", 1e-6),
+                                        device=getattr(self.args, "fedagg_device", None))
         if _defense(self.args) == dfn.DEFENSE_SLSGD:
             # defend_on_aggregation (slsgd_defense.py:54-67): the base operator, then the
             # moving average with the global model (extra_auxiliary_info, :81-85)

@@ -429,6 +429,38 @@ int fedagg_pairgram2_f32(const float* const* d_src, int32_t K,
                          const int64_t* d_chunks, int64_t n_chunks, double* d_out,
                          double* d_work, int64_t work_len, fedagg_stream_t stream);
 
+/* One Weiszfeld iteration of the geometric-median defense ("geomed";
+ * csrc/geomed.hip) in ONE pass over the K fp32 rows: the weighted sum z of
+ * the rows and every row's squared distance to z.  Only the columns of the
+ * chunk table count (the table fedagg_dist2_f32 takes: (start, length) int64
+ * pairs, 1 <= length <= FEDAGG_DIST_CHUNK, start of any alignment); a column
+ * outside the table is neither read nor written in d_z.
+ *   d_z[e], every table column e: the fedagg_wsum_f32 chain,
+ *     acc = fl32(src_0[e] * w_0); acc = fl32(acc + fl32(src_i[e] * w_i)),
+ *     clients in order, two separately rounded operations per step, never an
+ *     FMA: bit-identical to fedagg_wsum_f32 on the same inputs.
+ *   d_dist2[i] = sum over the table columns of (double)fl32(src_i[e] - d_z[e])^2:
+ *     the fp32 difference, its exact square in fp64 and an fp64 sum, i.e.
+ *     fedagg_dist2_f32's contract with ref = d_z.  The summation order is the
+ *     kernel's own but fixed: per-block partials go to d_work
+ *     (fedagg_robust_work_len(FEDAGG_WORK_WSUM_DIST2, K, n_chunks) doubles) and
+ *     are combined in a fixed order, without atomics, so two calls on the
+ *     same inputs give the same bits.  n_chunks == 0: d_dist2 = 0, d_z untouched.
+ * flags: FEDAGG_ALIGNED16 and FEDAGG_HOST_WEIGHTS as for fedagg_wsum_f32 (the
+ * kernel works one column per lane with 4-byte accesses, so aligned and
+ * unaligned calls run the same arithmetic).  Stream-ordered; allocates
+ * nothing and does not synchronise.  FEDAGG_EINVAL for K < 1, n_chunks < 0, a
+ * null pointer or work_len < K (checked before any HIP call); FEDAGG_ENOKERNEL
+ * for K > FEDAGG_GEOMED_MAX_CLIENTS: callers run fedagg_wsum_f32, then
+ * fedagg_dist2_f32 with ref = z. */
+#define FEDAGG_GEOMED_MAX_CLIENTS 128
+#define FEDAGG_WORK_WSUM_DIST2 3
+int fedagg_wsum_dist2_f32(const float* const* d_src, const float* d_w, int32_t K,
+                          const int64_t* d_chunks, int64_t n_chunks,
+                          float* d_z, double* d_dist2,
+                          double* d_work, int64_t work_len,
+                          uint32_t flags, fedagg_stream_t stream);
+
 /* The clipped rebuild of NormDiffClippingDefense (:38-54): over the first N
  * columns of every row,
  *   d_dst_i[e] = fl32( fl32( fl32(src_i[e] - ref[e]) / d_div[i] ) + ref[e] )
