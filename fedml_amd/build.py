@@ -17,7 +17,8 @@ SRC = os.path.join(HERE, "csrc", "fedagg.hip")
 # every translation unit of libfedagg.so: compiled to objects separately (an
 # unchanged unit is not recompiled), then linked
 SRCS = [SRC, os.path.join(HERE, "csrc", "robust.hip"), os.path.join(HERE, "csrc", "median.hip"),
-        os.path.join(HERE, "csrc", "trimmed.hip"), os.path.join(HERE, "csrc", "geomed.hip")]
+        os.path.join(HERE, "csrc", "trimmed.hip"), os.path.join(HERE, "csrc", "geomed.hip"),
+        os.path.join(HERE, "csrc", "nearmedian.hip")]
 # headers under csrc/ that the units share: a change rebuilds every unit
 CSRC_HEADERS = [os.path.join(HERE, "csrc", "sortnet.h")]
 OUT_DIR = os.path.join(HERE, "lib")

@@ -47,6 +47,18 @@ that are pure reductions over the client axis.
                 "geometric_median" / "RFA" loop (a Python set of weights, a
                 truncating zip) is NOT reproduced: those names stay refused.
 
+"wise_bulyan"   Not FedML's "bulyan" (which stays refused: its source is not
+                mirrored here): Bulyan (El Mhamdi, Guerraoui, Rouault, ICML
+                2018) under our own name and our own specification.  Stage 1
+                picks theta = K - 2f clients by repeated Krum on the K x K
+                squared distances of the weight keys (pairdist2_rows, computed
+                once; the rounds re-score on the host, bulyan_select).  Stage
+                2 averages, per coordinate of EVERY key, the beta = theta - 2f
+                selected values nearest the coordinate's median
+                (fedagg_nearmedian_mean_f32, specified in include/fedagg.h:
+                one launch over the whole row up to 128 selected clients, the
+                same rule in torch ops above that).  K >= 4f + 3.
+
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
                 the K x K squared distances of the clients' weight vectors are
@@ -111,9 +123,10 @@ DEFENSE_ROBUST_LEARNING_RATE = "robust_learning_rate"
 DEFENSE_WEAK_DP = "weak_dp"
 DEFENSE_WISE_TRIMMED_MEAN = "wise_trimmed_mean"  # not a FedML defense type: Yin et al.'s per-coordinate rule
 DEFENSE_GEOMED = "geomed"  # not a FedML defense type either: our geometric median (RFA), see geometric_median
+DEFENSE_WISE_BULYAN = "wise_bulyan"  # not FedML's "bulyan": our specification of Bulyan, see bulyan
 SUPPORTED = (DEFENSE_WISE_MEDIAN, DEFENSE_TRIMMED_MEAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_NORM_DIFF_CLIPPING,
              DEFENSE_SLSGD, DEFENSE_CCLIP, DEFENSE_ROBUST_LEARNING_RATE, DEFENSE_WEAK_DP, DEFENSE_WISE_TRIMMED_MEAN,
-             DEFENSE_GEOMED)
+             DEFENSE_GEOMED, DEFENSE_WISE_BULYAN)
 # FedMLDefender constructs these but lists them under none of its
 # before / on / after-aggregation hooks (fedml_defender.py:131-154), so the
 # plugin path aggregates as if no defense were set; they act only through
@@ -1091,3 +1104,198 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
             torch.cuda.current_stream().synchronize()  # the staging bucket goes out of scope
     out = OrderedDict((k, res[k]) for k in keys)
     return (out, info) if return_info else out
+
+
+# ---- Bulyan (csrc/nearmedian.hip) ----------------------------------------------
+
+NEARMEDIAN_MAX_CLIENTS = nat.NEARMEDIAN_MAX_CLIENTS  # fedagg_nearmedian_mean_f32 holds up to 128 rows
+
+
+def nearmedian_mean_rows(d_ptrs: torch.Tensor, K: int, N: int, keep: int, out: torch.Tensor) -> None:
+    """Per column the mean of the `keep` of K fp32 device rows' values nearest
+    the column's lower median (fedagg_nearmedian_mean_f32, specified in
+    include/fedagg.h): a contiguous rank window around the median, a tie
+    between a lower and a higher candidate going to the lower, summed in fp32
+    in ascending order and divided by keep.  K <= 128, 1 <= keep <= K."""
+    kn._require_cuda(out, "nearmedian_mean")
+    if out.dtype != torch.float32:
+        raise TypeError(f"nearmedian_mean: fp32 rows (got {out.dtype})")
+    nat.check(nat.lib().fedagg_nearmedian_mean_f32(d_ptrs.data_ptr(), K, N, keep, out.data_ptr(), 0,
+                                                   nat.stream_handle()), "nearmedian_mean")
+
+
+def nearmedian_mean_rows_torch(rows, keep: int, chunk_cols: "int | None" = None) -> torch.Tensor:
+    """The specification of fedagg_nearmedian_mean_f32 in torch ops, on any
+    device and for any K: the slow path above 128 selected rows.  rows: a
+    (K, N) fp32 tensor or a list of K fp32 rows of N elements.  Per column
+    chunk the order keys are sorted and mapped back to values; with NaN
+    standing as +inf the window start is lo_min plus the number of j in
+    [lo_min, lo_max) whose value is strictly farther from the median than the
+    value keep ranks above it (the two-pointer rule of the header, counted:
+    d(s[j]) falls and d(s[j + keep]) rises with j); the keep values are then
+    gathered and added one fp32 add per rank, and divided by a tensor holding
+    keep (see trimmed_mean_rows_torch).  chunk_cols: columns per chunk
+    (default: temporaries of about 1 GiB)."""
+    K = len(rows)
+    if K < 1:
+        raise ValueError("nearmedian mean of no rows")
+    if keep < 1 or keep > K:
+        raise ValueError(f"keep = {keep} of K = {K} rows")
+    r0 = rows[0]
+    if r0.dtype != torch.float32:
+        raise TypeError(f"nearmedian_mean: fp32 rows (got {r0.dtype})")
+    N = r0.numel()
+    if chunk_cols is None:
+        chunk_cols = max(1, (1 << 30) // (32 * K))
+    out = torch.empty(N, dtype=torch.float32, device=r0.device)
+    count = torch.full((1,), float(keep), dtype=torch.float32, device=r0.device)
+    r = (K - 1) // 2
+    lo_min, lo_max = max(0, r - keep + 1), min(r, K - keep)
+    inf = float("inf")
+    for c0 in range(0, N, chunk_cols):
+        c1 = min(N, c0 + chunk_cols)
+        x = rows[:, c0:c1] if isinstance(rows, torch.Tensor) else torch.stack([row[c0:c1] for row in rows])
+        keys = torch.sort(_order_keys(x.contiguous()), dim=0).values
+        s = (keys ^ ((keys >> 31) & 0x7FFFFFFF)).view(torch.float32)
+        nan = torch.isnan(s)
+        nans = nan.sum(dim=0)
+        sel = torch.where(nan, torch.full_like(s, inf), s)  # for the selection a NaN counts as +inf
+        m = sel[r]
+
+        def d(v):
+            return torch.where(v == m, torch.zeros_like(v), (v - m).abs())
+
+        lo = torch.full((c1 - c0,), lo_min, dtype=torch.int64, device=s.device)
+        if lo_max > lo_min:
+            lo += (d(sel[lo_min:lo_max]) > d(sel[lo_min + keep:lo_max + keep])).sum(dim=0)
+        acc = torch.gather(s, 0, lo[None, :])[0]  # the chain starts from the value, not from 0.0
+        for t in range(1, keep):
+            acc += torch.gather(s, 0, (lo + t)[None, :])[0]
+        res = acc / count
+        res[lo + keep > K - nans] = float("nan")  # the window holds a NaN
+        out[c0:c1] = res
+    return out
+
+
+def bulyan_select(D, f: int):
+    """Stage 1 of Bulyan on the host: theta = K - 2f clients by repeated Krum
+    over the K x K squared distances D (computed once; every round re-scores
+    from it).  R starts as all K clients; theta times, with n = |R|: for each
+    i in R the score is the float64 sum, in ascending order, of the
+    max(1, n - f - 2) smallest D[i][j] over j in R without i (NaN distances sort
+    last, above +inf; a NaN score ranks as +inf); the lowest score is picked,
+    ties going to the lowest client index, and moves from R to the selection.
+    A client that sends NaN makes its row and column of D NaN: sorted last, a
+    client with at most f such neighbours never sums one of them.  f = 0:
+    every client, in index order, without looking at D (scores of 0).
+    Returns (selected, scores): the clients in pick order and each pick's
+    score in its round."""
+    if f < 0:
+        raise ValueError("bulyan: byzantine_client_num must be >= 0")
+    K = len(D)
+    if f == 0:  # only D's length is looked at
+        return list(range(K)), [0.0] * K
+    D = np.asarray(D, dtype=np.float64)
+    theta = K - 2 * f
+    if theta < 1:
+        raise ValueError(f"bulyan: K = {K} clients leave no selection at f = {f}")
+    R = list(range(K))
+    selected, scores = [], []
+    for _ in range(theta):
+        n = len(R)
+        sub = D[np.ix_(R, R)].copy()
+        # the client itself goes last with the NaNs: never among the n - 1 others' first c
+        sub[np.arange(n), np.arange(n)] = np.nan
+        c = min(max(1, n - f - 2), n - 1)
+        if c < 1:  # a single client left: nothing to sum
+            sc = np.zeros(n)
+        else:
+            with np.errstate(invalid="ignore", over="ignore"):
+                sc = np.cumsum(np.sort(sub, axis=1)[:, :c], axis=1)[:, c - 1]  # sequential, ascending
+        sc = np.where(np.isnan(sc), np.inf, sc)
+        p = int(np.argmin(sc))  # the first of equal scores: R is ascending
+        selected.append(R[p])
+        scores.append(float(sc[p]))
+        del R[p]
+    return selected, scores
+
+
+class BulyanInfo:
+    """What bulyan did: the clients `selected` by stage 1 in pick order with
+    their `scores`, theta = K - 2f of them, `beta` = theta - 2f values kept
+    per coordinate, and the pair-distance `method` asked for."""
+
+    def __init__(self, selected, scores, theta: int, beta: int, method: str):
+        self.selected = list(selected)
+        self.scores = list(scores)
+        self.theta = theta
+        self.beta = beta
+        self.method = method
+
+    def __repr__(self):
+        return (f"BulyanInfo(selected={self.selected}, theta={self.theta}, beta={self.beta}, "
+                f"method={self.method!r})")
+
+
+def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_client_num: int, device=None,
+           method: str = "auto", return_info: bool = False):
+    """Bulyan (El Mhamdi, Guerraoui, Rouault; the "wise_bulyan" defense, ours:
+    FedML's own "bulyan" is not reproduced) with f = byzantine_client_num of K
+    clients, K >= 4f + 3.  Stage 1: theta = K - 2f clients by repeated Krum
+    (bulyan_select) on the squared distances of the weight keys, one
+    pairdist2_rows launch with `method` as Krum's.  Stage 2: per coordinate of
+    EVERY key (BatchNorm statistics and counters too, as wise_trimmed_mean)
+    the mean of the beta = theta - 2f selected values nearest the coordinate's
+    median: one fedagg_nearmedian_mean_f32 launch over the whole row through a
+    pointer table of the selected rows (nearmedian_mean_rows_torch above 128
+    selected clients).
+
+    fp32 models (integer buffers allowed, entering as fl32(v)).  Sample counts
+    are ignored, as by the median.  Returns a new OrderedDict in client 0's
+    key order on the inputs' device (integer keys come back fp32); no client
+    dict is modified.  return_info: also the BulyanInfo."""
+    f = byzantine_client_num
+    K = len(raw_client_grad_list)
+    if f < 0:
+        raise ValueError("bulyan: byzantine_client_num must be >= 0")
+    if K < 4 * f + 3:
+        raise ValueError(f"bulyan: byzantine_client_num = {f} needs at least 4f + 3 = {4 * f + 3} clients (got {K})")
+    if method not in ("auto", "gram", "exact"):
+        raise ValueError(f"pair distance method {method!r}: 'auto', 'gram' or 'exact'")
+    theta, beta = K - 2 * f, K - 4 * f
+    dicts = [raw_client_grad_list[i][1] for i in range(K)]
+    keys = list(dicts[0].keys())
+    for d in dicts[1:]:
+        for k in keys:
+            d[k]  # KeyError for a missing key
+    if not keys:
+        info = BulyanInfo(*bulyan_select(np.zeros((K, K)), f), theta, beta, method)
+        return (OrderedDict(), info) if return_info else OrderedDict()
+    _one_device(dicts[0], keys, "wise_bulyan")
+    on_dev = dicts[0][keys[0]].is_cuda
+    bucket, dev = _float_bucket(dicts[0], K, "wise_bulyan", device)
+    with torch.cuda.device(dev):
+        for i, d in enumerate(dicts):
+            _put_float(bucket, i, d, keys)
+        bucket.sync_ingest()
+        g = bucket.groups[torch.float32]
+        if f == 0:
+            selected, scores = bulyan_select(np.empty((K, 0)), 0)  # no distances needed
+        else:
+            chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
+            D = pairdist2_rows(g.d_ptrs, K, chunks, n_chunks, dev, method).cpu().numpy()
+            selected, scores = bulyan_select(D, f)
+        if theta <= NEARMEDIAN_MAX_CLIENTS:
+            ptrs = g.d_ptrs if selected == list(range(K)) else \
+                kn.upload_i64([g.rows[i].data_ptr() for i in selected], dev)
+            row = torch.zeros(g.padded, dtype=torch.float32, device=dev)
+            nearmedian_mean_rows(ptrs, theta, g.length, beta, row)
+        else:
+            row = nearmedian_mean_rows_torch([g.rows[i][:g.length] for i in selected], beta)
+        if not on_dev:
+            row = row.cpu()
+        res = {k: row[o:o + n].view(shp).clone() for k, o, n, shp in zip(g.keys, g.offsets, g.numels, g.shapes)}
+        if on_dev:
+            torch.cuda.current_stream().synchronize()  # the staging bucket goes out of scope
+    out = OrderedDict((k, res[k]) for k in keys)
+    return (out, BulyanInfo(selected, scores, theta, beta, method)) if return_info else out

@@ -12,7 +12,9 @@ reductions over the client axis and run on the GPU too (fedml_amd.defense):
 aggregation), dispatched exactly as FedMLDefender does
 (core/security/fedml_defender.py:131-171), and "wise_trimmed_mean", the
 per-coordinate trimmed mean FedML lacks, and "geomed", our geometric median
-(RFA; FedML's own "geometric_median" / "RFA" stay refused) (both on
+(RFA; FedML's own "geometric_median" / "RFA" stay refused), and "wise_bulyan",
+our Bulyan (repeated Krum, then per coordinate the mean of the values nearest
+the median; FedML's own "bulyan" stays refused) (all three on
 aggregation); so do the distance-based
 "krum" / "multikrum", "norm_diff_clipping", "slsgd" and "cclip".  "robust_learning_rate" and
 "weak_dp" are accepted and, as in FedML, leave the plugin path a plain FedAvg
@@ -53,6 +55,7 @@ _DEFENSE_ATTRS = {
     dfn.DEFENSE_CCLIP: ("bucket_size",),
     dfn.DEFENSE_SLSGD: ("trim_param_b",),  # then the alpha check, then option_type
     dfn.DEFENSE_WISE_TRIMMED_MEAN: ("beta",),  # ours, not FedML's: the per-coordinate trimmed mean
+    dfn.DEFENSE_WISE_BULYAN: ("byzantine_client_num",),  # ours, not FedML's "bulyan"
 }
 
 
@@ -153,6 +156,11 @@ class ServerAggregator(ABC):
                                         maxiter=getattr(self.args, "geomed_maxiter", 16),
                                         ftol=getattr(self.args, "geomed_ftol", 1e-6),
                                         device=getattr(self.args, "fedagg_device", None))
+        if _defense(self.args) == dfn.DEFENSE_WISE_BULYAN:
+            # not FedML's "bulyan": our Bulyan (repeated Krum, then the mean nearest the median) replaces the operator
+            return dfn.bulyan(raw_client_model_or_grad_list, self.args.byzantine_client_num,
+                              getattr(self.args, "fedagg_device", None),
+                              getattr(self.args, "fedagg_pair_distance", "auto"))
         if _defense(self.args) == dfn.DEFENSE_SLSGD:
             # defend_on_aggregation (slsgd_defense.py:54-67): the base operator, then the
             # moving average with the global model (extra_auxiliary_info, :81-85)

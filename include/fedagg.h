@@ -379,6 +379,49 @@ int fedagg_trimmed_mean(int32_t dtype, const void* const* d_src, int32_t K,
                         int64_t N, int32_t trim, void* d_out, uint32_t flags,
                         fedagg_stream_t stream);
 
+/* Mean of the values nearest the median: stage 2 of the "wise_bulyan" defense
+ * (Bulyan, El Mhamdi et al.; csrc/nearmedian.hip) over K fp32 rows, K being
+ * the number of rows handed in (Bulyan's theta), 1 <= keep <= K.  Every
+ * column independently:
+ *   1. Order.  Its K values are ordered by the total order of the selection
+ *      kernels, -inf < negatives < -0 < +0 < positives < +inf < every NaN;
+ *      s[0 .. K-1] is the column in that order, r = (K-1)/2 the lower-median
+ *      rank and m = s[r].
+ *   2. Distance.  For the selection only, a NaN counts as +inf, ranked above
+ *      the real +inf.  d(v) = 0 when v == m (IEEE equality: -0 and +0 are
+ *      equal, two equal infinities are equal), otherwise d(v) = fl32(|v - m|).
+ *      d is never NaN.
+ *   3. Window.  The kept values are the keep first elements of the merge of
+ *      the left side (s[r], s[r-1], ...) and the right side (s[r+1], ...) by
+ *      increasing d, a tie between a left and a right candidate going to the
+ *      LEFT.  As the two-pointer rule: start with l = h = r; keep - 1 times
+ *      take s[l-1] (l -= 1) if h == K-1, or if l > 0 and d(s[l-1]) <=
+ *      d(s[h+1]); otherwise take s[h+1] (h += 1).  The result is a contiguous
+ *      rank window [lo, lo + keep) that contains r.
+ *   4. Sum.  acc = s[lo], then acc = fl32(acc + s[j]) for j = lo+1 ..
+ *      lo+keep-1: one sequential fp32 chain in ascending rank order starting
+ *      from the value itself (an all -0 window stays -0).
+ *   5. Division.  out = fl32(acc / fl32(keep)), an IEEE-rounded division.
+ *   6. NaN.  If the window contains a NaN, that is lo + keep > K - (number of
+ *      NaNs), the output is a NaN of unspecified payload; this includes m
+ *      itself being a NaN.  A kept +inf with a kept -inf gives the
+ *      arithmetic's NaN.
+ * It follows that keep == K is the ascending mean, bit-identical to
+ * fedagg_trimmed_mean with trim 0, and that the result does not depend on the
+ * order of the rows.  The window is not centred in rank, so this is not a
+ * trimmed mean for keep < K.
+ * One lane per column in fedagg_trimmed_mean's form (K tiers 8 .. 128,
+ * launches of 2^30 columns, every alignment).  Stream-ordered; allocates
+ * nothing and does not synchronise; flags is reserved.  Checked before any
+ * HIP call: FEDAGG_EINVAL for K < 1, N < 0, keep < 1, keep > K or a null
+ * pointer; FEDAGG_ENOKERNEL for K > FEDAGG_NEARMEDIAN_MAX_CLIENTS (callers
+ * run the same rule in torch ops above it); N == 0 returns FEDAGG_OK without
+ * a launch. */
+#define FEDAGG_NEARMEDIAN_MAX_CLIENTS 128
+int fedagg_nearmedian_mean_f32(const float* const* d_src, int32_t K, int64_t N,
+                               int32_t keep, float* d_out, uint32_t flags,
+                               fedagg_stream_t stream);
+
 /* Distance-based defenses (csrc/robust.hip).  Rows are K fp32 device
  * pointers; the columns that count (FedML's vectorize_weight: every key but
  * BatchNorm running stats and counters, core/security/common/utils.py:8-21)
