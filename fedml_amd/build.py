@@ -20,7 +20,7 @@ SRCS = [SRC, os.path.join(HERE, "csrc", "robust.hip"), os.path.join(HERE, "csrc"
         os.path.join(HERE, "csrc", "trimmed.hip"), os.path.join(HERE, "csrc", "geomed.hip"),
         os.path.join(HERE, "csrc", "nearmedian.hip")]
 # headers under csrc/ that the units share: a change rebuilds every unit
-CSRC_HEADERS = [os.path.join(HERE, "csrc", "sortnet.h")]
+CSRC_HEADERS = [os.path.join(HERE, "csrc", "sortnet.h"), os.path.join(HERE, "csrc", "host_util.h")]
 OUT_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(OUT_DIR, "obj")
 OUT = os.path.join(OUT_DIR, "libfedagg.so")

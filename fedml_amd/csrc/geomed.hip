@@ -34,20 +34,12 @@
 #include <string>
 
 #include "../../include/fedagg.h"
+#include "host_util.h"
 
-extern "C" int fedagg_set_error_internal(int code, const char* msg);
 extern "C" __attribute__((visibility("hidden"))) int64_t fedagg_wsum_dist2_work_len_internal(int32_t K,
                                                                                              int64_t n_chunks);
 
 namespace {
-
-int set_error(int code, const std::string& msg) { return fedagg_set_error_internal(code, msg.c_str()); }
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(static_cast<int>(e), std::string(what) + ": " + hipGetErrorString(e));
-  return FEDAGG_OK;
-}
 
 constexpr int kBS = 256;
 constexpr int kWaves = kBS / 64;

@@ -13,6 +13,7 @@
 #include <utility>
 
 #include "../../include/fedagg.h"
+#include "host_util.h"
 #include "sortnet.h"
 
 // 1 would keep the mirrored-pair merge (a lane select per cross-lane step) in
@@ -27,17 +28,7 @@ constexpr int kPk16Batch = 2;
 // (profiles/r03/lanes_nt/)
 constexpr int kLanesNT = 0;
 
-extern "C" int fedagg_set_error_internal(int code, const char* msg);
-
 namespace {
-
-int set_error(int code, const std::string& msg) { return fedagg_set_error_internal(code, msg.c_str()); }
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(static_cast<int>(e), std::string(what) + ": " + hipGetErrorString(e));
-  return FEDAGG_OK;
-}
 
 // loads of the lane-group kernels (kLanesNT)
 template <class T>
@@ -75,7 +66,7 @@ __device__ typename E::S g_median_pad[2] = {__builtin_bit_cast(typename E::S, st
                                                 sizeof(typename E::S) == 4, uint32_t, uint16_t>>(E::kPosInf))};
 
 // Columns [col0, col0 + N) of the rows; out points at column col0's slot.
-// Launches cover at most 2^30 columns (kMedianChunk) so that a lane's byte
+// Launches cover at most 2^30 columns (kColsChunk) so that a lane's byte
 // offset from the (wave-uniform) row base + col0 fits in 32 bits.
 template <int KMAX, bool FULL, int BS, bool PRIO = false, class E = MedF32, bool OFF = false>
 __global__ __launch_bounds__(BS) void median_kernel(const typename E::S* const* __restrict__ src, int K, int64_t N,
@@ -103,32 +94,10 @@ __global__ __launch_bounds__(BS) void median_kernel(const typename E::S* const* 
   typename E::NanAcc nacc{};
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) {
-    // Keep at most 16 row pointers live in SGPRs: without the barrier the
-    // scheduler hoists all K pointer loads to the top and spills them.
+    // the load form and the barrier: load_slot (sortnet.h).  All KMAX loads
+    // are in flight before the first value is used.
     if (c % 16 == 0 && c) __builtin_amdgcn_sched_barrier(0);
-    // A padded slot (c >= K) reads a ±inf constant: its row pointer is the
-    // pad and its lane offset is 0, so the load itself yields the pad.
-    // Nothing per slot waits for a load here: all KMAX loads are in flight
-    // before the first value is used.
-    const bool live = FULL || c < K;
-    const typename E::S* p;
-    if constexpr (FULL) {
-      p = src[c];
-    } else {
-      // readfirstlane returns int: go through uint32_t, or a low word with
-      // its top bit set sign-extends over the high word
-      const uint64_t t = reinterpret_cast<uint64_t>(tab[c]);
-      const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t >> 32))));
-      const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t))));
-      p = reinterpret_cast<const typename E::S*>((uint64_t(hi) << 32) | uint64_t(lo));
-    }
-    const char __attribute__((address_space(1)))* row;
-    if constexpr (OFF)
-      row = live ? row_base(p, col0) : reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
-    else
-      row = reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
-    v[c] = E::widen(cols_load(
-        reinterpret_cast<const typename E::S __attribute__((address_space(1)))*>(row + (live ? boff : 0u))));
+    v[c] = E::widen(load_slot<FULL, OFF>(src, tab, c, K, boff, col0));
     if constexpr (sizeof(typename E::S) == 2) E::nan_add(nacc, v[c]);
   }
   // torch returns the first NaN of the column (client order) if there is
@@ -177,25 +146,12 @@ __global__ __launch_bounds__(BS) void median_kernel(const typename E::S* const* 
   out[e] = has_nan ? nan_raw : E::narrow(v[(KMAX - 1) / 2]);
 }
 
-constexpr int64_t kMedianChunk = int64_t(1) << 30;  // columns per launch of the 32-bit-offset kernels
-
 template <int KMAX, class E = MedF32>
 int launch_median(const typename E::S* const* src, int K, int64_t N, typename E::S* out, hipStream_t st) {
   constexpr int BS = 64;  // 3 % faster than 256 at config 3 (tools/median_probe.py, two boxes)
-  for (int64_t c0 = 0; c0 < N; c0 += kMedianChunk) {
-    const int64_t n = N - c0 < kMedianChunk ? N - c0 : kMedianChunk;
-    const int64_t grid = (n + BS - 1) / BS;
-    if (K == KMAX && c0 == 0)
-      hipLaunchKernelGGL((median_kernel<KMAX, true, BS, false, E>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
-                         out, c0);
-    else if (c0 == 0)
-      hipLaunchKernelGGL((median_kernel<KMAX, false, BS, false, E>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
-                         out, c0);
-    else  // past 2^30 columns: the padded kernel (correct for K == KMAX too) with the row offset
-      hipLaunchKernelGGL((median_kernel<KMAX, false, BS, false, E, true>), dim3(unsigned(grid)), dim3(BS), 0, st, src,
-                         K, n, out + c0, c0);
-  }
-  return check_launch("fedagg_median");
+  return launch_col_chunks("fedagg_median", median_kernel<KMAX, true, BS, false, E>,
+                           median_kernel<KMAX, false, BS, false, E>, median_kernel<KMAX, false, BS, false, E, true>,
+                           K == KMAX, BS, 1, st, src, K, N, out);
 }
 
 // 16-bit rows, K <= 128, two columns per lane: a 32-bit load brings columns
@@ -299,20 +255,10 @@ __global__ __launch_bounds__(BS) void median_pk16_kernel(const uint16_t* const* 
 template <int KMAX, class E>
 int launch_median_pk16(const uint16_t* const* src, int K, int64_t N, uint16_t* out, hipStream_t st) {
   constexpr int BS = 64;
-  for (int64_t c0 = 0; c0 < N; c0 += kMedianChunk) {  // even chunk starts: 4-byte pairs stay aligned
-    const int64_t n = N - c0 < kMedianChunk ? N - c0 : kMedianChunk;
-    const int64_t grid = ((n + 1) / 2 + BS - 1) / BS;
-    if (K == KMAX && c0 == 0)
-      hipLaunchKernelGGL((median_pk16_kernel<KMAX, true, E, BS>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
-                         out, c0);
-    else if (c0 == 0)
-      hipLaunchKernelGGL((median_pk16_kernel<KMAX, false, E, BS>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
-                         out, c0);
-    else
-      hipLaunchKernelGGL((median_pk16_kernel<KMAX, false, E, BS, true>), dim3(unsigned(grid)), dim3(BS), 0, st, src,
-                         K, n, out + c0, c0);
-  }
-  return check_launch("fedagg_median");
+  // two columns per thread; the even chunk starts keep the 4-byte pairs aligned
+  return launch_col_chunks("fedagg_median", median_pk16_kernel<KMAX, true, E, BS>,
+                           median_pk16_kernel<KMAX, false, E, BS>, median_pk16_kernel<KMAX, false, E, BS, true>,
+                           K == KMAX, BS, 2, st, src, K, N, out);
 }
 
 // More than 128 clients, in registers: P adjacent lanes share one column,
@@ -1294,14 +1240,7 @@ int median_dispatch(const typename E::S* const* d_src, int32_t K, int64_t N, typ
       return launch_median_pk16_lanes<1, 128, E, 256, true>(d_src, K, N, d_out, st);
     }
   }
-  if (K <= 8) return launch_median<8, E>(d_src, K, N, d_out, st);
-  if (K <= 16) return launch_median<16, E>(d_src, K, N, d_out, st);
-  if (K <= 24) return launch_median<24, E>(d_src, K, N, d_out, st);
-  if (K <= 32) return launch_median<32, E>(d_src, K, N, d_out, st);
-  if (K <= 48) return launch_median<48, E>(d_src, K, N, d_out, st);
-  if (K <= 64) return launch_median<64, E>(d_src, K, N, d_out, st);
-  if (K <= 96) return launch_median<96, E>(d_src, K, N, d_out, st);
-  return launch_median<128, E>(d_src, K, N, d_out, st);
+  return with_tier(K, [&](auto kmax, auto) { return launch_median<decltype(kmax)::value, E>(d_src, K, N, d_out, st); });
 }
 
 

@@ -12,19 +12,10 @@
 #include <utility>
 
 #include "../../include/fedagg.h"
+#include "host_util.h"
 #include "sortnet.h"
 
-extern "C" int fedagg_set_error_internal(int code, const char* msg);
-
 namespace {
-
-int set_error(int code, const std::string& msg) { return fedagg_set_error_internal(code, msg.c_str()); }
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(static_cast<int>(e), std::string(what) + ": " + hipGetErrorString(e));
-  return FEDAGG_OK;
-}
 
 // +inf: what a padded slot's load returns
 __device__ float g_nearmedian_pad = __builtin_huge_valf();
@@ -122,27 +113,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void ne
   float v[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) {
-    // at most 16 row pointers live in SGPRs (see median_kernel)
+    // the load form and the barrier: load_slot (sortnet.h)
     if (c % 16 == 0 && c) __builtin_amdgcn_sched_barrier(0);
-    const bool live = FULL || c < K;
-    const float* p;
-    if constexpr (FULL) {
-      p = src[c];
-    } else {
-      // readfirstlane returns int: through uint32_t, or a low word with its
-      // top bit set sign-extends over the high word
-      const uint64_t t = reinterpret_cast<uint64_t>(tab[c]);
-      const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t >> 32))));
-      const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t))));
-      p = reinterpret_cast<const float*>((uint64_t(hi) << 32) | uint64_t(lo));
-    }
-    const char __attribute__((address_space(1)))* row;
-    if constexpr (OFF)
-      row = live ? row_base(p, col0) : reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
-    else
-      row = reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
-    // a padded slot reads the +inf constant: lane offset 0 on the pad's address
-    v[c] = cols_load(reinterpret_cast<const float __attribute__((address_space(1)))*>(row + (live ? boff : 0u)));
+    v[c] = load_slot<FULL, OFF>(src, tab, c, K, boff, col0);
   }
   // after every load is in flight: one unordered compare, a count and a
   // select per value
@@ -191,25 +164,13 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void ne
   out[e] = lo + keep > K - nans ? __builtin_nanf("") : mean;
 }
 
-constexpr int64_t kNearmedianChunk = int64_t(1) << 30;  // columns per launch of the 32-bit-offset kernel
-
 template <int KMAX, int KMIN>
 int launch_nearmedian(const float* const* src, int K, int64_t N, int keep, float* out, hipStream_t st) {
   constexpr int BS = 64;  // the median kernel's block (median.hip launch_median)
-  for (int64_t c0 = 0; c0 < N; c0 += kNearmedianChunk) {
-    const int64_t n = N - c0 < kNearmedianChunk ? N - c0 : kNearmedianChunk;
-    const int64_t grid = (n + BS - 1) / BS;
-    if (K == KMAX && c0 == 0)
-      hipLaunchKernelGGL((nearmedian_mean_kernel<KMAX, KMIN, true, BS>), dim3(unsigned(grid)), dim3(BS), 0, st, src,
-                         K, n, keep, out, c0);
-    else if (c0 == 0)
-      hipLaunchKernelGGL((nearmedian_mean_kernel<KMAX, KMIN, false, BS>), dim3(unsigned(grid)), dim3(BS), 0, st,
-                         src, K, n, keep, out, c0);
-    else  // past 2^30 columns: the padded kernel (correct for K == KMAX too) with the row offset
-      hipLaunchKernelGGL((nearmedian_mean_kernel<KMAX, KMIN, false, BS, true>), dim3(unsigned(grid)), dim3(BS), 0,
-                         st, src, K, n, keep, out + c0, c0);
-  }
-  return check_launch("fedagg_nearmedian_mean_f32");
+  return launch_col_chunks("fedagg_nearmedian_mean_f32", nearmedian_mean_kernel<KMAX, KMIN, true, BS>,
+                           nearmedian_mean_kernel<KMAX, KMIN, false, BS>,
+                           nearmedian_mean_kernel<KMAX, KMIN, false, BS, true>, K == KMAX, BS, 1, st, src, K, N, out,
+                           keep);
 }
 
 }  // namespace
@@ -229,15 +190,10 @@ int fedagg_nearmedian_mean_f32(const float* const* d_src, int32_t K, int64_t N, 
                                            std::to_string(K) + ")");
   if (N == 0) return FEDAGG_OK;
   auto st = reinterpret_cast<hipStream_t>(stream);
-  // the tiers of fedagg_trimmed_mean; KMIN is the smallest K a tier is launched for
-  if (K <= 8) return launch_nearmedian<8, 1>(d_src, K, N, keep, d_out, st);
-  if (K <= 16) return launch_nearmedian<16, 9>(d_src, K, N, keep, d_out, st);
-  if (K <= 24) return launch_nearmedian<24, 17>(d_src, K, N, keep, d_out, st);
-  if (K <= 32) return launch_nearmedian<32, 25>(d_src, K, N, keep, d_out, st);
-  if (K <= 48) return launch_nearmedian<48, 33>(d_src, K, N, keep, d_out, st);
-  if (K <= 64) return launch_nearmedian<64, 49>(d_src, K, N, keep, d_out, st);
-  if (K <= 96) return launch_nearmedian<96, 65>(d_src, K, N, keep, d_out, st);
-  return launch_nearmedian<128, 97>(d_src, K, N, keep, d_out, st);
+  // KMIN, the smallest K a tier is launched for, bounds the ranks the median can take
+  return with_tier(K, [&](auto kmax, auto kmin) {
+    return launch_nearmedian<decltype(kmax)::value, decltype(kmin)::value>(d_src, K, N, keep, d_out, st);
+  });
 }
 
 }  // extern "C"

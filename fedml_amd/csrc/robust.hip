@@ -34,20 +34,11 @@
 #include <string>
 
 #include "../../include/fedagg.h"
+#include "host_util.h"
 
-
-extern "C" int fedagg_set_error_internal(int code, const char* msg);
 extern "C" int64_t fedagg_wsum_dist2_work_len_internal(int32_t K, int64_t n_chunks);
 
 namespace {
-
-int rset(int code, const std::string& msg) { return fedagg_set_error_internal(code, msg.c_str()); }
-
-int rcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rset(static_cast<int>(e), std::string(what) + ": " + hipGetErrorString(e));
-  return FEDAGG_OK;
-}
 
 template <class T>
 __device__ __forceinline__ const T __attribute__((address_space(1)))* gptr(const T* p) {
@@ -1137,13 +1128,13 @@ int pair_tiles(int K) { const int T = (K + kPT - 1) / kPT; return T * (T + 1) / 
 template <bool MUL>
 int launch_diff(const char* what, const float* const* d_src, int32_t K, const float* d_ref, const float* d_c, int64_t N,
                 float* const* d_dst, fedagg_stream_t stream) {
-  if (K < 1 || N < 0) return rset(FEDAGG_EINVAL, std::string(what) + ": K must be >= 1 and N >= 0");
-  if (!d_src || !d_ref || !d_c || !d_dst) return rset(FEDAGG_EINVAL, std::string(what) + ": null pointer");
+  if (K < 1 || N < 0) return set_error(FEDAGG_EINVAL, std::string(what) + ": K must be >= 1 and N >= 0");
+  if (!d_src || !d_ref || !d_c || !d_dst) return set_error(FEDAGG_EINVAL, std::string(what) + ": null pointer");
   if (N == 0) return FEDAGG_OK;
   const int G = grid_groups(2, (N + FEDAGG_DIST_CHUNK - 1) / FEDAGG_DIST_CHUNK, 0, 0);
   hipLaunchKernelGGL((clip_diff_kernel<MUL, kClipClients>), dim3(unsigned(G)), dim3(kBS), 0,
                      static_cast<hipStream_t>(stream), d_src, K, d_ref, d_c, N, d_dst, G);
-  return rcheck(what);
+  return check_launch(what);
 }
 
 }  // namespace
@@ -1173,35 +1164,35 @@ int64_t fedagg_robust_work_len(int32_t kind, int32_t K, int64_t n_chunks) {
 
 int fedagg_dist2_f32(const float* const* d_src, int32_t K, const float* d_ref, const int64_t* d_chunks,
                      int64_t n_chunks, double* d_out, double* d_work, int64_t work_len, fedagg_stream_t stream) {
-  if (K < 1 || n_chunks < 0) return rset(FEDAGG_EINVAL, "fedagg_dist2_f32: K must be >= 1 and n_chunks >= 0");
+  if (K < 1 || n_chunks < 0) return set_error(FEDAGG_EINVAL, "fedagg_dist2_f32: K must be >= 1 and n_chunks >= 0");
   if (!d_src || !d_out || (n_chunks > 0 && (!d_chunks || !d_work)))
-    return rset(FEDAGG_EINVAL, "fedagg_dist2_f32: null pointer");
+    return set_error(FEDAGG_EINVAL, "fedagg_dist2_f32: null pointer");
   auto st = static_cast<hipStream_t>(stream);
   if (n_chunks == 0) {
-    if (hipMemsetAsync(d_out, 0, sizeof(double) * K, st) != hipSuccess) return rcheck("fedagg_dist2_f32");
+    if (hipMemsetAsync(d_out, 0, sizeof(double) * K, st) != hipSuccess) return check_launch("fedagg_dist2_f32");
     return FEDAGG_OK;
   }
-  if (work_len < K) return rset(FEDAGG_EINVAL, "fedagg_dist2_f32: workspace smaller than K doubles");
+  if (work_len < K) return set_error(FEDAGG_EINVAL, "fedagg_dist2_f32: workspace smaller than K doubles");
   const int G = grid_groups(4, n_chunks, work_len, K);
   hipLaunchKernelGGL(dist2_kernel, dim3(unsigned(G)), dim3(kBS), 0, st, d_src, K, d_ref, d_chunks, n_chunks, G,
                      d_work);
   hipLaunchKernelGGL(sum_rows_kernel, dim3(unsigned(K)), dim3(256), 0, st, d_work, G, d_out);
-  return rcheck("fedagg_dist2_f32");
+  return check_launch("fedagg_dist2_f32");
 }
 
 int fedagg_pairdist2_f32(const float* const* d_src, int32_t K, const int64_t* d_chunks, int64_t n_chunks,
                          double* d_out, double* d_work, int64_t work_len, fedagg_stream_t stream) {
-  if (K < 1 || n_chunks < 0) return rset(FEDAGG_EINVAL, "fedagg_pairdist2_f32: K must be >= 1 and n_chunks >= 0");
+  if (K < 1 || n_chunks < 0) return set_error(FEDAGG_EINVAL, "fedagg_pairdist2_f32: K must be >= 1 and n_chunks >= 0");
   if (!d_src || !d_out || (n_chunks > 0 && (!d_chunks || !d_work)))
-    return rset(FEDAGG_EINVAL, "fedagg_pairdist2_f32: null pointer");
+    return set_error(FEDAGG_EINVAL, "fedagg_pairdist2_f32: null pointer");
   auto st = static_cast<hipStream_t>(stream);
   if (n_chunks == 0) {
-    if (hipMemsetAsync(d_out, 0, sizeof(double) * K * K, st) != hipSuccess) return rcheck("fedagg_pairdist2_f32");
+    if (hipMemsetAsync(d_out, 0, sizeof(double) * K * K, st) != hipSuccess) return check_launch("fedagg_pairdist2_f32");
     return FEDAGG_OK;
   }
   if (K <= kTriMax) {  // the whole triangle in one block per chunk group
     const int64_t per = int64_t(16) * tri_blocks(K);
-    if (work_len < per) return rset(FEDAGG_EINVAL, "fedagg_pairdist2_f32: workspace too small (fedagg_robust_work_len)");
+    if (work_len < per) return set_error(FEDAGG_EINVAL, "fedagg_pairdist2_f32: workspace too small (fedagg_robust_work_len)");
     const int G = grid_groups(4, n_chunks, work_len, per);
     if (K <= 64)
       hipLaunchKernelGGL(pairtri_kernel<16>, dim3(unsigned(G)), dim3(unsigned(tri_threads(K))), 0, st, d_src, K,
@@ -1210,34 +1201,34 @@ int fedagg_pairdist2_f32(const float* const* d_src, int32_t K, const int64_t* d_
       hipLaunchKernelGGL(pairtri_kernel<32>, dim3(unsigned(G)), dim3(unsigned(tri_threads(K))), 0, st, d_src, K,
                          d_chunks, n_chunks, G, d_work);
     hipLaunchKernelGGL(tri_finish_kernel, dim3(unsigned((per + 63) / 64)), dim3(256), 0, st, d_work, G, K, d_out);
-    return rcheck("fedagg_pairdist2_f32");
+    return check_launch("fedagg_pairdist2_f32");
   }
   const int NT = pair_tiles(K);
   if (work_len < int64_t(NT) * kPT * kPT)
-    return rset(FEDAGG_EINVAL, "fedagg_pairdist2_f32: workspace too small (fedagg_robust_work_len)");
+    return set_error(FEDAGG_EINVAL, "fedagg_pairdist2_f32: workspace too small (fedagg_robust_work_len)");
   const int G = grid_groups(NT, n_chunks, work_len, int64_t(NT) * kPT * kPT);
   hipLaunchKernelGGL(pairdist_kernel, dim3(unsigned(NT), unsigned(G)), dim3(kBS), 0, st, d_src, K, d_chunks, n_chunks,
                      G, d_work);
   hipLaunchKernelGGL(pair_finish_kernel, dim3(unsigned(kPT * kPT / 64), unsigned(NT)), dim3(256), 0, st, d_work, G,
                      K, d_out);
-  return rcheck("fedagg_pairdist2_f32");
+  return check_launch("fedagg_pairdist2_f32");
 }
 
 int fedagg_pairgram2_f32(const float* const* d_src, int32_t K, const int64_t* d_chunks, int64_t n_chunks,
                          double* d_out, double* d_work, int64_t work_len, fedagg_stream_t stream) {
   if (K < 1 || K > kGramMax || n_chunks < 0)
-    return rset(FEDAGG_EINVAL, "fedagg_pairgram2_f32: K must be in [1, 128] and n_chunks >= 0");
+    return set_error(FEDAGG_EINVAL, "fedagg_pairgram2_f32: K must be in [1, 128] and n_chunks >= 0");
   if (!d_src || !d_out || (n_chunks > 0 && (!d_chunks || !d_work)))
-    return rset(FEDAGG_EINVAL, "fedagg_pairgram2_f32: null pointer");
+    return set_error(FEDAGG_EINVAL, "fedagg_pairgram2_f32: null pointer");
   auto st = static_cast<hipStream_t>(stream);
   if (n_chunks == 0) {
-    if (hipMemsetAsync(d_out, 0, sizeof(double) * K * K, st) != hipSuccess) return rcheck("fedagg_pairgram2_f32");
+    if (hipMemsetAsync(d_out, 0, sizeof(double) * K * K, st) != hipSuccess) return check_launch("fedagg_pairgram2_f32");
     return FEDAGG_OK;
   }
   const int64_t per = int64_t(gram_tiles(K)) * 256;
   const int64_t mat = int64_t(K) * K;
   if (work_len < per + mat)
-    return rset(FEDAGG_EINVAL, "fedagg_pairgram2_f32: workspace too small (fedagg_robust_work_len)");
+    return set_error(FEDAGG_EINVAL, "fedagg_pairgram2_f32: workspace too small (fedagg_robust_work_len)");
   int G = grid_groups(4096 / (256 * kGramBlocksPerCU), n_chunks, work_len - mat, per);
   double* M = d_work + int64_t(G) * per;
   {
@@ -1258,7 +1249,7 @@ int fedagg_pairgram2_f32(const float* const* d_src, int32_t K, const int64_t* d_
   }
   hipLaunchKernelGGL(gram_sum_kernel, dim3(unsigned((per + 63) / 64)), dim3(256), 0, st, d_work, G, K, M);
   hipLaunchKernelGGL(gram_dist_kernel, dim3(unsigned((mat + 255) / 256)), dim3(256), 0, st, M, K, d_out);
-  return rcheck("fedagg_pairgram2_f32");
+  return check_launch("fedagg_pairgram2_f32");
 }
 
 int fedagg_clip_diff_f32(const float* const* d_src, int32_t K, const float* d_ref, const float* d_div, int64_t N,

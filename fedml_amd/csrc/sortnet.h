@@ -1,13 +1,18 @@
 // sortnet.h — what the one-lane-per-column selection kernels share: the
 // compile-time pairwise sorting network, the element types (fp32, bf16, f16
-// as fp32 "selection values") and the row loads.  Included by median.hip and
-// trimmed.hip; everything is internal to the including translation unit.
+// as fp32 "selection values"), the per-slot row load (load_slot) and, on the
+// host, the chunked launch (launch_col_chunks) and the tier ladder (with_tier).
+// Included by median.hip, trimmed.hip and nearmedian.hip; everything is
+// internal to the including translation unit.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <utility>
+
+#include "host_util.h"
 
 // Loads of the one-lane-per-column kernels (K <= 128; 256 B per wave
 // instruction): 1 non-temporal, 0 plain
@@ -189,6 +194,92 @@ __device__ __forceinline__ const char __attribute__((address_space(1)))* row_bas
   uint64_t b = reinterpret_cast<uint64_t>(p) + uint64_t(col0) * sizeof(T);
   asm("" : "+s"(b));
   return reinterpret_cast<const char __attribute__((address_space(1)))*>(b);
+}
+
+// The raw value of slot c for the lane at byte offset boff of the rows: the
+// one load form of median_kernel, trimmed_mean_kernel and
+// nearmedian_mean_kernel.  The kernel's unrolled loop over the slots, its
+// widening and its NaN handling stay with the kernel, and so does the
+//   if (c % 16 == 0 && c) __builtin_amdgcn_sched_barrier(0);
+// in front of each call, which keeps at most 16 row pointers live in SGPRs:
+// without it the scheduler hoists all KMAX pointer loads to the top and
+// spills them.
+//   - FULL (K == KMAX): the row pointer is src[c], a scalar load.
+//   - Padded tiers read it from tab, the block's LDS table of KMAX slot
+//     pointers (pads point at a ±inf constant), at a wave-uniform address and
+//     move it to SGPRs.  readfirstlane returns int: each half goes through
+//     uint32_t, or a low word with its top bit set sign-extends over the high
+//     word.
+//   - A padded slot (c >= K) reads the pad constant: its row pointer is the
+//     pad and its lane offset is 0, so the load itself yields the pad and
+//     nothing per slot waits for a load.
+//   - OFF (launches past 2^30 columns): a live row's base is row_base(p, col0),
+//     the opaque SGPR pair that keeps the SGPR-base + 32-bit-offset form; a
+//     pad is read at its own address.
+// src carries no __restrict__ here (the kernels' own parameter does): with it
+// the K = 8 full fp32 median kernel allocated its SGPRs differently (26 -> 28);
+// without it every kernel's assembly is what the written-out block gave.
+template <bool FULL, bool OFF, class S, int NT>
+__device__ __forceinline__ S load_slot(const S* const* src, const S* const (&tab)[NT], int c, int K, uint32_t boff,
+                                       int64_t col0) {
+  const bool live = FULL || c < K;
+  const S* p;
+  if constexpr (FULL) {
+    p = src[c];
+  } else {
+    const uint64_t t = reinterpret_cast<uint64_t>(tab[c]);
+    const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t >> 32))));
+    const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t))));
+    p = reinterpret_cast<const S*>((uint64_t(hi) << 32) | uint64_t(lo));
+  }
+  const char __attribute__((address_space(1)))* row;
+  if constexpr (OFF)
+    row = live ? row_base(p, col0) : reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
+  else
+    row = reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
+  return cols_load(reinterpret_cast<const S __attribute__((address_space(1)))*>(row + (live ? boff : 0u)));
+}
+
+// ---------------------------------------------------------------------------
+// Host side of the one-lane-per-column kernels.
+
+// Columns per launch: a lane's byte offset from the (wave-uniform) row base +
+// col0 fits in 32 bits.  Even, so the 4-byte column pairs of the packed
+// 16-bit kernel stay aligned at every chunk start.
+constexpr int64_t kColsChunk = int64_t(1) << 30;
+
+// Columns [0, N) in launches of at most kColsChunk columns, each thread taking
+// `per_thread` adjacent columns: kernel(src, K, n, mid..., out + c0, c0) for
+// every chunk start c0.  The first chunk runs `full` when K is the tier's KMAX
+// and `padded` otherwise; the chunks past 2^30 columns run `padded_off`, the
+// padded kernel (correct for K == KMAX too) with the row offset.
+template <class Kern, class S, class... Mid>
+int launch_col_chunks(const char* what, Kern full, Kern padded, Kern padded_off, bool is_full, int BS, int per_thread,
+                      hipStream_t st, const S* const* src, int K, int64_t N, S* out, Mid... mid) {
+  for (int64_t c0 = 0; c0 < N; c0 += kColsChunk) {
+    const int64_t n = N - c0 < kColsChunk ? N - c0 : kColsChunk;
+    const int64_t grid = ((n + per_thread - 1) / per_thread + BS - 1) / BS;
+    const Kern kernel = c0 ? padded_off : is_full ? full : padded;
+    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n, mid..., out + c0, c0);
+  }
+  return check_launch(what);
+}
+
+// The tiers of the kernels' KMAX.  with_tier calls f(KMAX, KMIN) as
+// std::integral_constant<int, ..> values for the smallest tier holding K
+// (the last for anything above it: the callers bound K); KMIN is the smallest
+// K the tier is chosen for, the previous tier + 1.
+constexpr int kTiers[] = {8, 16, 24, 32, 48, 64, 96, 128};
+constexpr int kNumTiers = int(sizeof(kTiers) / sizeof(kTiers[0]));
+
+template <int I = 0, class F>
+int with_tier(int K, F f) {
+  constexpr int KMAX = kTiers[I], KMIN = I ? kTiers[I ? I - 1 : 0] + 1 : 1;
+  // this tier's call stands before the next tier's: the kernels are emitted in ascending tier order
+  if (K <= KMAX || I + 1 == kNumTiers)
+    return f(std::integral_constant<int, KMAX>{}, std::integral_constant<int, KMIN>{});
+  if constexpr (I + 1 < kNumTiers) return with_tier<I + 1>(K, f);
+  __builtin_unreachable();
 }
 
 }  // namespace

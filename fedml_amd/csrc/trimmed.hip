@@ -12,19 +12,10 @@
 #include <type_traits>
 
 #include "../../include/fedagg.h"
+#include "host_util.h"
 #include "sortnet.h"
 
-extern "C" int fedagg_set_error_internal(int code, const char* msg);
-
 namespace {
-
-int set_error(int code, const std::string& msg) { return fedagg_set_error_internal(code, msg.c_str()); }
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(static_cast<int>(e), std::string(what) + ": " + hipGetErrorString(e));
-  return FEDAGG_OK;
-}
 
 // ---------------------------------------------------------------------------
 // The median kernel's form (median.hip: one lane per column, the column's K
@@ -83,7 +74,7 @@ template <class E>
 __device__ typename E::S g_trimmed_pad = trim_pos_inf<E>();
 
 // Columns [col0, col0 + N) of the rows; out points at column col0's slot.
-// Launches cover at most 2^30 columns (kTrimmedChunk) so that a lane's byte
+// Launches cover at most 2^30 columns (kColsChunk) so that a lane's byte
 // offset from the (wave-uniform) row base + col0 fits in 32 bits.
 template <int KMAX, bool FULL, int BS, class E, bool OFF = false>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void trimmed_mean_kernel(const typename E::S* const* __restrict__ src, int K,
@@ -106,27 +97,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void tr
   int nans = 0;
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) {
-    // at most 16 row pointers live in SGPRs (see median_kernel)
+    // the load form and the barrier: load_slot (sortnet.h)
     if (c % 16 == 0 && c) __builtin_amdgcn_sched_barrier(0);
-    const bool live = FULL || c < K;
-    const S* p;
-    if constexpr (FULL) {
-      p = src[c];
-    } else {
-      // readfirstlane returns int: through uint32_t, or a low word with its
-      // top bit set sign-extends over the high word
-      const uint64_t t = reinterpret_cast<uint64_t>(tab[c]);
-      const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t >> 32))));
-      const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(t))));
-      p = reinterpret_cast<const S*>((uint64_t(hi) << 32) | uint64_t(lo));
-    }
-    const char __attribute__((address_space(1)))* row;
-    if constexpr (OFF)
-      row = live ? row_base(p, col0) : reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
-    else
-      row = reinterpret_cast<const char __attribute__((address_space(1)))*>(as_global(p));
-    // a padded slot reads the +inf constant: lane offset 0 on the pad's address
-    S x = cols_load(reinterpret_cast<const S __attribute__((address_space(1)))*>(row + (live ? boff : 0u)));
+    S x = load_slot<FULL, OFF>(src, tab, c, K, boff, col0);
     if constexpr (sizeof(S) == 2) {
       // 16-bit rows test the raw value as it widens (holding every raw value
       // until all loads have landed would double the live registers)
@@ -167,38 +140,19 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void tr
   out[e] = TrimVal<E>::round(nans > trim ? __builtin_nanf("") : mean);
 }
 
-constexpr int64_t kTrimmedChunk = int64_t(1) << 30;  // columns per launch of the 32-bit-offset kernel
-
 template <int KMAX, class E>
 int launch_trimmed(const typename E::S* const* src, int K, int64_t N, int trim, typename E::S* out, hipStream_t st) {
   constexpr int BS = 64;  // the median kernel's block (median.hip launch_median)
-  for (int64_t c0 = 0; c0 < N; c0 += kTrimmedChunk) {
-    const int64_t n = N - c0 < kTrimmedChunk ? N - c0 : kTrimmedChunk;
-    const int64_t grid = (n + BS - 1) / BS;
-    if (K == KMAX && c0 == 0)
-      hipLaunchKernelGGL((trimmed_mean_kernel<KMAX, true, BS, E>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
-                         trim, out, c0);
-    else if (c0 == 0)
-      hipLaunchKernelGGL((trimmed_mean_kernel<KMAX, false, BS, E>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n,
-                         trim, out, c0);
-    else  // past 2^30 columns: the padded kernel (correct for K == KMAX too) with the row offset
-      hipLaunchKernelGGL((trimmed_mean_kernel<KMAX, false, BS, E, true>), dim3(unsigned(grid)), dim3(BS), 0, st, src,
-                         K, n, trim, out + c0, c0);
-  }
-  return check_launch("fedagg_trimmed_mean");
+  return launch_col_chunks("fedagg_trimmed_mean", trimmed_mean_kernel<KMAX, true, BS, E>,
+                           trimmed_mean_kernel<KMAX, false, BS, E>, trimmed_mean_kernel<KMAX, false, BS, E, true>,
+                           K == KMAX, BS, 1, st, src, K, N, out, trim);
 }
 
 template <class E>
 int trimmed_dispatch(const typename E::S* const* d_src, int32_t K, int64_t N, int32_t trim, typename E::S* d_out,
                      hipStream_t st) {
-  if (K <= 8) return launch_trimmed<8, E>(d_src, K, N, trim, d_out, st);
-  if (K <= 16) return launch_trimmed<16, E>(d_src, K, N, trim, d_out, st);
-  if (K <= 24) return launch_trimmed<24, E>(d_src, K, N, trim, d_out, st);
-  if (K <= 32) return launch_trimmed<32, E>(d_src, K, N, trim, d_out, st);
-  if (K <= 48) return launch_trimmed<48, E>(d_src, K, N, trim, d_out, st);
-  if (K <= 64) return launch_trimmed<64, E>(d_src, K, N, trim, d_out, st);
-  if (K <= 96) return launch_trimmed<96, E>(d_src, K, N, trim, d_out, st);
-  return launch_trimmed<128, E>(d_src, K, N, trim, d_out, st);
+  return with_tier(
+      K, [&](auto kmax, auto) { return launch_trimmed<decltype(kmax)::value, E>(d_src, K, N, trim, d_out, st); });
 }
 
 }  // namespace

@@ -152,6 +152,34 @@ def _one_device(d0, wkeys, what: str) -> None:
             f"gathers every client onto one GPU, so run it on a round that fits one device")
 
 
+def _client_dicts(raw_client_grad_list, want=None) -> Tuple[list, list]:
+    """The clients' dicts and client 0's keys (those `want` accepts; None: all),
+    each looked up in every other client: KeyError for a missing key."""
+    dicts = [raw_client_grad_list[i][1] for i in range(len(raw_client_grad_list))]
+    keys = [k for k in dicts[0].keys() if want is None or want(k)]
+    for d in dicts[1:]:
+        for k in keys:
+            d[k]
+    return dicts, keys
+
+
+def _rows_to_dict(rows, keys, on_device: bool, clone: bool) -> "OrderedDict":
+    """Finished rows of a staging bucket as a new OrderedDict in `keys` order.
+    rows: (group, row) pairs, consumed one by one (a generator may launch the
+    next group's kernel only then).  Host inputs get host tensors back; clone:
+    every key its own storage instead of a view of the row.  Call on the
+    bucket's device: the stream is drained before the bucket goes out of scope."""
+    res = {}
+    for g, row in rows:
+        if not on_device:
+            row = row.cpu()
+        for k, o, n, shp in zip(g.keys, g.offsets, g.numels, g.shapes):
+            res[k] = row[o:o + n].view(shp).clone() if clone else row[o:o + n].view(shp)
+    if on_device:
+        torch.cuda.current_stream().synchronize()
+    return OrderedDict((k, res[k]) for k in keys)
+
+
 def median_f32(d_ptrs: torch.Tensor, K: int, N: int, out: torch.Tensor) -> None:
     """Coordinate-wise lower median of K fp32 device rows (fedagg_median_f32)."""
     kn._require_cuda(out, "median_f32")
@@ -196,11 +224,7 @@ def coordinate_wise_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"
                            ) -> "OrderedDict":
     """CoordinateWiseMedianDefense.defend_on_aggregation on the GPU."""
     K = len(raw_client_grad_list)
-    dicts = [raw_client_grad_list[i][1] for i in range(K)]
-    wkeys = [k for k in dicts[0].keys() if is_weight_param(k)]
-    for d in dicts[1:]:
-        for k in wkeys:
-            d[k]  # KeyError for a missing key, as vectorize_weight would fail
+    dicts, wkeys = _client_dicts(raw_client_grad_list, is_weight_param)  # the keys of vectorize_weight
     t0 = dicts[0][wkeys[0]] if wkeys else None
     if t0 is None:
         raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")  # vectorize_weight on no keys
@@ -350,11 +374,7 @@ def coordinate_wise_trimmed_mean(raw_client_grad_list: List[Tuple[float, "Ordere
     trim = int(beta * K)
     if K - 2 * trim < 1:
         raise ValueError(f"beta = {beta} trims every one of {K} clients")
-    dicts = [raw_client_grad_list[i][1] for i in range(K)]
-    keys = list(dicts[0].keys())
-    for d in dicts[1:]:
-        for k in keys:
-            d[k]  # KeyError for a missing key
+    dicts, keys = _client_dicts(raw_client_grad_list)
     if not keys:
         return OrderedDict()
     _one_device(dicts[0], keys, "wise_trimmed_mean")
@@ -363,7 +383,6 @@ def coordinate_wise_trimmed_mean(raw_client_grad_list: List[Tuple[float, "Ordere
                                         torch.device("cuda", torch.cuda.current_device()))
     floats = {torch.float32, torch.bfloat16, torch.float16}
     row_dt = trimmed_row_dtype(dicts[0][k].dtype for k in keys)
-    result = {}
     with torch.cuda.device(dev):
         # 16-bit keys of a promoted model are declared fp32: put() widens them
         layout = [(k, tuple(dicts[0][k].shape), row_dt if dicts[0][k].dtype in floats else dicts[0][k].dtype)
@@ -372,19 +391,17 @@ def coordinate_wise_trimmed_mean(raw_client_grad_list: List[Tuple[float, "Ordere
         for i in range(K):
             bucket.put(i, {k: dicts[i][k] for k in keys}, 1)
         bucket.sync_ingest()
-        for g in bucket.groups.values():  # the float keys' row; integer keys in an fp32 row
-            if K <= TRIMMED_MAX_CLIENTS:
-                row = torch.empty(g.padded, dtype=g.dtype, device=dev)
-                trimmed_mean_rows(g.d_ptrs, K, g.length, trim, row, aligned=True)
-            else:
-                row = trimmed_mean_rows_torch(g.rows[:, :g.length], trim)
-            if not t0.is_cuda:
-                row = row.cpu()
-            for k, o, n, shp in zip(g.keys, g.offsets, g.numels, g.shapes):
-                result[k] = row[o:o + n].view(shp)
-        if t0.is_cuda:
-            torch.cuda.current_stream().synchronize()  # the staging bucket goes out of scope
-    return OrderedDict((k, result[k]) for k in keys)
+
+        def rows():
+            for g in bucket.groups.values():  # the float keys' row; integer keys in an fp32 row
+                if K <= TRIMMED_MAX_CLIENTS:
+                    row = torch.empty(g.padded, dtype=g.dtype, device=dev)
+                    trimmed_mean_rows(g.d_ptrs, K, g.length, trim, row, aligned=True)
+                else:
+                    row = trimmed_mean_rows_torch(g.rows[:, :g.length], trim)
+                yield g, row
+
+        return _rows_to_dict(rows(), keys, t0.is_cuda, clone=False)
 
 
 # ---- distance-based defenses (csrc/robust.hip) ---------------------------------
@@ -1038,11 +1055,7 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
     K = len(raw_client_grad_list)
     if K < 1:
         raise ValueError("geomed: no clients")
-    dicts = [raw_client_grad_list[i][1] for i in range(K)]
-    keys = list(dicts[0].keys())
-    for d in dicts[1:]:
-        for k in keys:
-            d[k]  # KeyError for a missing key
+    dicts, keys = _client_dicts(raw_client_grad_list)
     total = 0
     for n, _ in raw_client_grad_list:
         total += n
@@ -1097,12 +1110,7 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
             w32 = [float(np.float32(w[i])) for i in alive]
             kn.wsum_ptrs(torch.float32, table(alive), kn.weights_for(w32, torch.float32, dev), len(alive), g.length,
                          row, True)
-        if not on_dev:
-            row = row.cpu()
-        res = {k: row[o:o + n].view(shp).clone() for k, o, n, shp in zip(g.keys, g.offsets, g.numels, g.shapes)}
-        if on_dev:
-            torch.cuda.current_stream().synchronize()  # the staging bucket goes out of scope
-    out = OrderedDict((k, res[k]) for k in keys)
+        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
     return (out, info) if return_info else out
 
 
@@ -1263,11 +1271,7 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
     if method not in ("auto", "gram", "exact"):
         raise ValueError(f"pair distance method {method!r}: 'auto', 'gram' or 'exact'")
     theta, beta = K - 2 * f, K - 4 * f
-    dicts = [raw_client_grad_list[i][1] for i in range(K)]
-    keys = list(dicts[0].keys())
-    for d in dicts[1:]:
-        for k in keys:
-            d[k]  # KeyError for a missing key
+    dicts, keys = _client_dicts(raw_client_grad_list)
     if not keys:
         info = BulyanInfo(*bulyan_select(np.zeros((K, K)), f), theta, beta, method)
         return (OrderedDict(), info) if return_info else OrderedDict()
@@ -1292,10 +1296,5 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
             nearmedian_mean_rows(ptrs, theta, g.length, beta, row)
         else:
             row = nearmedian_mean_rows_torch([g.rows[i][:g.length] for i in selected], beta)
-        if not on_dev:
-            row = row.cpu()
-        res = {k: row[o:o + n].view(shp).clone() for k, o, n, shp in zip(g.keys, g.offsets, g.numels, g.shapes)}
-        if on_dev:
-            torch.cuda.current_stream().synchronize()  # the staging bucket goes out of scope
-    out = OrderedDict((k, res[k]) for k in keys)
+        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
     return (out, BulyanInfo(selected, scores, theta, beta, method)) if return_info else out

@@ -66,7 +66,8 @@ def test_check_catches_a_removed_guard(tmp_path):
     obj = tmp_path / "robust_noguard.o"
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                     "-fno-gpu-flush-denormals-to-zero", "-fhip-fp32-correctly-rounded-divide-sqrt",
-                    "--cuda-device-only", "-c", "-o", str(obj), str(d / "robust.hip")], check=True, timeout=600)
+                    "--cuda-device-only", "-I" + os.path.dirname(SRC),  # the unit's own headers (host_util.h)
+                    "-c", "-o", str(obj), str(d / "robust.hip")], check=True, timeout=600)
     res = mh.check(str(obj))
     gram = {k: v for k, v in res.items() if "pairgram_split8_kernel" in k}
     assert len(gram) == 8
