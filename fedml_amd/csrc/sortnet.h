@@ -8,7 +8,9 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
+#include <string>
 #include <type_traits>
 #include <utility>
 
@@ -246,18 +248,47 @@ __device__ __forceinline__ S load_slot(const S* const* src, const S* const (&tab
 // Columns per launch: a lane's byte offset from the (wave-uniform) row base +
 // col0 fits in 32 bits.  Even, so the 4-byte column pairs of the packed
 // 16-bit kernel stay aligned at every chunk start.
+// The environment variable FEDAGG_COLS_CHUNK (cols_chunk below) replaces it
+// for a call: it exists for the tests, which run the kernels of the later
+// launches on a few hundred columns.
 constexpr int64_t kColsChunk = int64_t(1) << 30;
 
-// Columns [0, N) in launches of at most kColsChunk columns, each thread taking
-// `per_thread` adjacent columns: kernel(src, K, n, mid..., out + c0, c0) for
-// every chunk start c0.  The first chunk runs `full` when K is the tier's KMAX
-// and `padded` otherwise; the chunks past 2^30 columns run `padded_off`, the
-// padded kernel (correct for K == KMAX too) with the row offset.
+// The columns per launch of this call: kColsChunk, or FEDAGG_COLS_CHUNK where
+// it is set and not empty.  Read on every call (as FEDAGG_PACK_SPAWN is in
+// fedagg.hip), so one process can switch it.  The whole string must be a
+// decimal integer, even (the packed kernel's column pairs) and in
+// [2, kColsChunk] (the 32-bit byte offset); anything else is FEDAGG_EINVAL,
+// never a silent default.
+inline int cols_chunk(const char* what, int64_t& chunk) {
+  chunk = kColsChunk;
+  const char* s = getenv("FEDAGG_COLS_CHUNK");
+  if (!s || !*s) return FEDAGG_OK;
+  int64_t v = 0;
+  bool ok = true;
+  for (const char* p = s; *p && ok; ++p) {
+    ok = *p >= '0' && *p <= '9' && v <= kColsChunk;  // v stays far below overflow
+    if (ok) v = v * 10 + (*p - '0');
+  }
+  if (!ok || v < 2 || v > kColsChunk || (v & 1))
+    return set_error(FEDAGG_EINVAL, std::string(what) + ": FEDAGG_COLS_CHUNK must be an even decimal integer in [2, " +
+                                        std::to_string(kColsChunk) + "] (got \"" + s + "\")");
+  chunk = v;
+  return FEDAGG_OK;
+}
+
+// Columns [0, N) in launches of at most cols_chunk() columns, each thread
+// taking `per_thread` adjacent columns: kernel(src, K, n, mid..., out + c0, c0)
+// for every chunk start c0.  The first chunk runs `full` when K is the tier's
+// KMAX and `padded` otherwise; the later chunks (past 2^30 columns) run
+// `padded_off`, the padded kernel (correct for K == KMAX too) with the row
+// offset.
 template <class Kern, class S, class... Mid>
 int launch_col_chunks(const char* what, Kern full, Kern padded, Kern padded_off, bool is_full, int BS, int per_thread,
                       hipStream_t st, const S* const* src, int K, int64_t N, S* out, Mid... mid) {
-  for (int64_t c0 = 0; c0 < N; c0 += kColsChunk) {
-    const int64_t n = N - c0 < kColsChunk ? N - c0 : kColsChunk;
+  int64_t chunk;
+  if (int rc = cols_chunk(what, chunk)) return rc;  // before the first launch
+  for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+    const int64_t n = N - c0 < chunk ? N - c0 : chunk;
     const int64_t grid = ((n + per_thread - 1) / per_thread + BS - 1) / BS;
     const Kern kernel = c0 ? padded_off : is_full ? full : padded;
     hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(BS), 0, st, src, K, n, mid..., out + c0, c0);

@@ -2,8 +2,9 @@
 the two-pointer reference (tests/bulyan_ref.py), bit for bit: every K tier in
 its full and padded form, planted NaN / inf / tie columns, every small column
 over a small alphabet, the defense end to end and the torch path above 128
-selected clients.  The 2^30-column offset variant of the kernel is compiled but
-not launched here."""
+selected clients.  The offset variant of the kernel (the launches past 2^30
+columns) runs in tests/test_gpu_col_chunks.py, at every tier, on launches of
+130 columns; a launch at the true 2^30 boundary is run by no test."""
 from __future__ import annotations
 
 from collections import OrderedDict

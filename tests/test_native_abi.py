@@ -77,6 +77,50 @@ def test_argument_validation_without_gpu(lib):
     assert lib.fedagg_wsum_fedopt_optrepo_f32(9, 1, 1, 1, 1, 1, 1, 1, 1, 0, None) == -1
 
 
+@pytest.mark.parametrize("value", ["3", "0", "-2", "1073741826", "12x", " "])
+def test_cols_chunk_override_is_validated_without_gpu(lib, monkeypatch, value):
+    """FEDAGG_COLS_CHUNK (csrc/sortnet.h, the launch chunk of the column
+    kernels, for the tests): a value that is no even decimal integer in
+    [2, 2^30] is FEDAGG_EINVAL in each of the three units that launch through
+    launch_col_chunks, before any HIP call, and names the variable and the
+    value: a mistyped value must not quietly test nothing."""
+    monkeypatch.setenv("FEDAGG_COLS_CHUNK", value)
+    p = 64  # never dereferenced: the check stands before the first launch
+    calls = {
+        "fedagg_median": lambda: lib.fedagg_median(nat.DT_F32, p, 3, 10, p, 0, None),
+        "fedagg_trimmed_mean": lambda: lib.fedagg_trimmed_mean(nat.DT_F32, p, 3, 10, 1, p, 0, None),
+        "fedagg_nearmedian_mean_f32": lambda: lib.fedagg_nearmedian_mean_f32(p, 3, 10, 2, p, 0, None),
+    }
+    for name, call in calls.items():
+        lib.fedagg_trimmed_mean(nat.DT_F32, p, 3, 10, 5, p, 0, None)  # another error in between
+        assert b"trim must be" in lib.fedagg_last_error()
+        assert call() == -1, name  # FEDAGG_EINVAL
+        msg = lib.fedagg_last_error()
+        assert msg.startswith(name.encode() + b": FEDAGG_COLS_CHUNK") and b'"' + value.encode() + b'"' in msg, msg
+
+
+def test_cols_chunk_override_leaves_argument_validation_alone(lib, monkeypatch):
+    """With a valid chunk set the entry points validate their arguments as
+    before (K = 200: the median's lane-group path, which does not chunk)."""
+    monkeypatch.setenv("FEDAGG_COLS_CHUNK", "130")
+    p = 64
+    assert lib.fedagg_median(nat.DT_F32, p, 200, 0, p, 0, None) == 0  # N == 0: nothing to do
+    assert lib.fedagg_median(nat.DT_F32, p, 200, -1, p, 0, None) == -1
+    assert b"K must be >= 1 and N >= 0" in lib.fedagg_last_error()
+    assert lib.fedagg_median(nat.DT_F32, None, 200, 10, p, 0, None) == -1
+    assert b"null pointer" in lib.fedagg_last_error()
+    assert lib.fedagg_median(nat.DT_F32, p, 0, 10, p, 0, None) == -1
+    assert lib.fedagg_trimmed_mean(nat.DT_F32, p, 200, 10, 1, p, 0, None) == -2  # FEDAGG_ENOKERNEL
+    assert b"at most" in lib.fedagg_last_error()
+    assert lib.fedagg_nearmedian_mean_f32(p, 3, 10, 4, p, 0, None) == -1
+    assert b"keep must be" in lib.fedagg_last_error()
+    # an invalid chunk does not shadow them either: the arguments are checked first
+    monkeypatch.setenv("FEDAGG_COLS_CHUNK", "3")
+    assert lib.fedagg_median(nat.DT_F32, None, 3, 10, p, 0, None) == -1
+    assert b"null pointer" in lib.fedagg_last_error()
+    assert lib.fedagg_median(nat.DT_F32, p, 3, 0, p, 0, None) == 0
+
+
 def test_multi_block_plan(lib):
     from fedml_amd.kernels import MultiF32Plan
 
