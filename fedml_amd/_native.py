@@ -27,6 +27,7 @@ DT_F32, DT_BF16, DT_F16, DT_F64, DT_I64, DT_I32 = 0, 1, 2, 3, 4, 5
 DIST_CHUNK, PAIR_CHUNK = 1024, 256  # FEDAGG_DIST_CHUNK / FEDAGG_PAIR_CHUNK
 WORK_DIST2, WORK_PAIRDIST2, WORK_PAIRGRAM, WORK_WSUM_DIST2 = 0, 1, 2, 3
 TRIMMED_MAX_CLIENTS = 128  # FEDAGG_TRIMMED_MAX_CLIENTS
+TRIMMED_WIDE_MAX_CLIENTS = 1024  # FEDAGG_TRIMMED_WIDE_MAX_CLIENTS
 GEOMED_MAX_CLIENTS = 128  # FEDAGG_GEOMED_MAX_CLIENTS
 NEARMEDIAN_MAX_CLIENTS = 128  # FEDAGG_NEARMEDIAN_MAX_CLIENTS
 # FEDAGG_FEDOPT_*: the launch kinds of fedagg_wsum_fedopt_batch (besides the FEDAGG_OPT_* codes)
@@ -82,6 +83,7 @@ SIGNATURES = {
     "fedagg_median_f32": (ctypes.c_int, [_P, _I32, _I64, _P, _U32, _P]),
     "fedagg_median": (ctypes.c_int, [_I32, _P, _I32, _I64, _P, _U32, _P]),
     "fedagg_trimmed_mean": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
+    "fedagg_trimmed_mean_wide": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_nearmedian_mean_f32": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_sum_mod_i64": (ctypes.c_int, [_P, _I32, _I64, _I64, _P, _U32, _P]),
     "fedagg_lsa_reconstruct_f32": (ctypes.c_int, [_P, _I32, _I64, _P, _I64, _I32, _F, _P, _U32, _P]),

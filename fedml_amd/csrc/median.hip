@@ -14,6 +14,7 @@
 
 #include "../../include/fedagg.h"
 #include "host_util.h"
+#include "lanesort.h"
 #include "sortnet.h"
 
 // 1 would keep the mirrored-pair merge (a lane select per cross-lane step) in
@@ -21,23 +22,9 @@
 constexpr int kPk16Mirror = 0;
 // reversed DPP reads issued per batch in lanes4_merge_median
 constexpr int kPk16Batch = 2;
-// Loads of the lane-group kernels: a wave instruction reads 64 B of each of P
-// rows' 128-B lines and the block's next wave reads the other half, so plain
-// loads (0) keep the line in L2 for it; non-temporal ones (1) fetched 1.04-1.5x
-// the algorithmic bytes vs 1.00-1.03x, at the same time
-// (profiles/r03/lanes_nt/)
-constexpr int kLanesNT = 0;
+// kLanesNT, the load form of the lane-group kernels: lanesort.h
 
 namespace {
-
-// loads of the lane-group kernels (kLanesNT)
-template <class T>
-__device__ __forceinline__ T lanes_load(const T __attribute__((address_space(1)))* p) {
-  if constexpr (kLanesNT)
-    return __builtin_nontemporal_load(p);
-  else
-    return *p;
-}
 
 // ---------------------------------------------------------------------------
 // Coordinate-wise median (the reference's "wise_median" defense:
@@ -281,83 +268,9 @@ int launch_median_pk16(const uint16_t* const* src, int K, int64_t N, uint16_t* o
 // the padded median slot KMAX/2 - 1, i.e. it is the column's lower median.
 // VALU per column ≈ 8k (P·R = 4·64), 20k (4·128), 49k (8·128) lane-ops,
 // against 2k for K <= 128.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-__device__ __forceinline__ short2_t dpp_mov(short2_t x) {
-  return __builtin_bit_cast(short2_t, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
-template <int M>
-constexpr int dpp_xor_ctrl() {
-  static_assert(M == 1 || M == 2 || M == 3 || M == 7 || M == 15, "lane xor pattern without a single DPP mov");
-  // quad_perm [1,0,3,2], [2,3,0,1], [3,2,1,0]; row_half_mirror; row_mirror
-  return M == 1 ? 0xB1 : M == 2 ? 0x4E : M == 3 ? 0x1B : M == 7 ? 0x141 : 0x140;
-}
-
-// The value of lane ^ M: one DPP mov where a pattern exists (xor 1, 2, 3,
-// 7, 15), two for xor 4 (xor 7 then xor 3), else ds_bpermute (xor 31: the
-// last level of the 32-lane groups above 2,048 clients).
-template <int M>
-constexpr bool dpp_xor_ok() { return M == 1 || M == 2 || M == 3 || M == 7 || M == 15; }
-template <int M>
-__device__ __forceinline__ float xor_mov(float x) {
-  if constexpr (dpp_xor_ok<M>()) return dpp_mov<dpp_xor_ctrl<M>()>(x);
-  else if constexpr (M == 4) return dpp_mov<dpp_xor_ctrl<3>()>(dpp_mov<dpp_xor_ctrl<7>()>(x));  // (i ^ 7) ^ 3
-  else return __int_as_float(__shfl_xor(__float_as_int(x), M, 64));
-}
-
-// min (lower lanes, sel = -inf) or max (upper lanes, sel = +inf) of own
-// register i and the partner lane's register R-1-i, for every i
-template <int M, int R>
-__device__ __forceinline__ void lanes_reverse_pair(float (&v)[R], float sel) {
-  // opaque to the compiler: knowing sel is ±inf it splits every v_med3 into
-  // min, max and a select (three ops and twice the live registers)
-  asm volatile("" : "+v"(sel));
-#pragma unroll
-  for (int i = 0; i < R / 2; ++i) {
-    const float a = xor_mov<M>(v[R - 1 - i]);
-    const float b = xor_mov<M>(v[i]);
-    v[i] = __builtin_amdgcn_fmed3f(v[i], a, sel);
-    v[R - 1 - i] = __builtin_amdgcn_fmed3f(v[R - 1 - i], b, sel);
-  }
-}
-
-// half-cleaner stage between lanes sub and sub ^ M, same register
-template <int M, int R>
-__device__ __forceinline__ void lanes_cross_stage(float (&v)[R], int sub) {
-  float sel = (sub & M) ? __builtin_huge_valf() : -__builtin_huge_valf();
-  asm volatile("" : "+v"(sel));
-#pragma unroll
-  for (int i = 0; i < R; ++i) v[i] = __builtin_amdgcn_fmed3f(v[i], xor_mov<M>(v[i]), sel);
-}
-
-// in-lane half-cleaner cascade: a bitonic register array -> ascending
-template <int R>
-__device__ __forceinline__ void lane_bitonic_merge(float (&v)[R]) {
-#pragma unroll
-  for (int d = R / 2; d > 0; d /= 2) {
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-      if ((i & d) == 0) cmpx(v[i], v[i + d]);
-  }
-}
-
-// merge levels G = 2, 4, 8 (< P): afterwards every group of G lanes holds its
-// G·R values sorted ascending over slots (sub % G)·R + j
-template <int G, int P, int R>
-__device__ __forceinline__ void lanes_merge_levels(float (&v)[R], int sub) {
-  if constexpr (G < P) {
-    static_assert(G <= 16, "lane groups of at most 32");
-    lanes_reverse_pair<G - 1>(v, (sub & (G / 2)) ? __builtin_huge_valf() : -__builtin_huge_valf());
-    if constexpr (G == 16) lanes_cross_stage<4>(v, sub);  // slot distance 4R
-    if constexpr (G >= 8) lanes_cross_stage<2>(v, sub);  // slot distance 2R
-    if constexpr (G >= 4) lanes_cross_stage<1>(v, sub);  // slot distance R
-    lane_bitonic_merge(v);
-    lanes_merge_levels<G * 2, P, R>(v, sub);
-  }
-}
+// dpp_mov, xor_mov, lanes_reverse_pair, lanes_cross_stage, lane_bitonic_merge
+// and lanes_merge_levels: lanesort.h (shared with trimmed_wide.hip, which runs
+// the last level in full)
 
 // Four lanes per column (P = 4), odd lanes in the reversed order
 // (complemented int16 keys), every lane's run sorted ascending in its own

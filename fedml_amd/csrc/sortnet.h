@@ -2,7 +2,8 @@
 // compile-time pairwise sorting network, the element types (fp32, bf16, f16
 // as fp32 "selection values"), the per-slot row load (load_slot) and, on the
 // host, the chunked launch (launch_col_chunks) and the tier ladder (with_tier).
-// Included by median.hip, trimmed.hip and nearmedian.hip; everything is
+// Included by median.hip, trimmed.hip, trimmed_wide.hip and nearmedian.hip
+// (and by lanesort.h, the lane-group sort above 128 clients); everything is
 // internal to the including translation unit.
 #pragma once
 
@@ -186,6 +187,41 @@ struct MedF16 {
   static __device__ __forceinline__ bool nan_any(NanAcc a) { return a; }
   static constexpr uint32_t kNegInf = 0xfc00u, kPosInf = 0x7c00u;
 };
+
+// The trimmed mean kernels (trimmed.hip, trimmed_wide.hip):
+// what the chain adds for a sorted selection value, and the final rounding
+template <class E>
+struct TrimVal;
+template <>
+struct TrimVal<MedF32> {
+  static __device__ __forceinline__ float value(float v) { return v; }
+  static __device__ __forceinline__ float round(float f) { return f; }
+};
+template <>
+struct TrimVal<MedBF16> {
+  static __device__ __forceinline__ float value(float v) { return v; }  // bf16 widened exactly
+  static __device__ __forceinline__ uint16_t round(float f) {
+    const __bf16 b = static_cast<__bf16>(f);  // v_cvt_pk_bf16_f32: RNE
+    return __builtin_bit_cast(uint16_t, b);
+  }
+};
+template <>
+struct TrimVal<MedF16> {
+  // the selection value is an order key: back to the f16 bits, then v_cvt_f32_f16
+  static __device__ __forceinline__ float value(float v) {
+    return static_cast<float>(__builtin_bit_cast(_Float16, MedF16::narrow(v)));
+  }
+  static __device__ __forceinline__ uint16_t round(float f) {
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));  // v_cvt_f16_f32: RNE
+  }
+};
+
+template <class E>
+using raw_bits_t = std::conditional_t<sizeof(typename E::S) == 4, uint32_t, uint16_t>;
+template <class E>
+constexpr typename E::S trim_pos_inf() {
+  return __builtin_bit_cast(typename E::S, static_cast<raw_bits_t<E>>(E::kPosInf));
+}
 
 // Row base of client row p for a launch starting at column col0 (> 0 only
 // past 2^30 columns): an opaque SGPR pair, so the loads keep the

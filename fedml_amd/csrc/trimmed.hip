@@ -35,39 +35,8 @@ namespace {
 // wave-uniform predicate trim <= r < K - trim, so no register array is
 // indexed by a runtime value.
 
-// what the chain adds for a sorted selection value, and the final rounding
-template <class E>
-struct TrimVal;
-template <>
-struct TrimVal<MedF32> {
-  static __device__ __forceinline__ float value(float v) { return v; }
-  static __device__ __forceinline__ float round(float f) { return f; }
-};
-template <>
-struct TrimVal<MedBF16> {
-  static __device__ __forceinline__ float value(float v) { return v; }  // bf16 widened exactly
-  static __device__ __forceinline__ uint16_t round(float f) {
-    const __bf16 b = static_cast<__bf16>(f);  // v_cvt_pk_bf16_f32: RNE
-    return __builtin_bit_cast(uint16_t, b);
-  }
-};
-template <>
-struct TrimVal<MedF16> {
-  // the selection value is an order key: back to the f16 bits, then v_cvt_f32_f16
-  static __device__ __forceinline__ float value(float v) {
-    return static_cast<float>(__builtin_bit_cast(_Float16, MedF16::narrow(v)));
-  }
-  static __device__ __forceinline__ uint16_t round(float f) {
-    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));  // v_cvt_f16_f32: RNE
-  }
-};
-
-template <class E>
-using raw_bits_t = std::conditional_t<sizeof(typename E::S) == 4, uint32_t, uint16_t>;
-template <class E>
-constexpr typename E::S trim_pos_inf() {
-  return __builtin_bit_cast(typename E::S, static_cast<raw_bits_t<E>>(E::kPosInf));
-}
+// TrimVal (what the chain adds for a sorted selection value, and the final
+// rounding) and trim_pos_inf: sortnet.h, shared with trimmed_wide.hip
 
 // +inf in each element type: what a padded slot's load returns
 template <class E>

@@ -30,9 +30,10 @@ that are pure reductions over the client axis.
                 element of every key drops its int(beta * K) smallest and
                 largest client values and averages the rest
                 (fedagg_trimmed_mean, specified in include/fedagg.h: one
-                launch per row group up to 128 clients, the same rule in torch
-                ops above that; BatchNorm statistics included, integer keys
-                as fl32(v)).  Up to int(beta * K) clients sending anything,
+                launch per row group up to 128 clients, one launch of
+                fedagg_trimmed_mean_wide from 129 to 1024 clients, the same
+                rule in torch ops above that; BatchNorm statistics included,
+                integer keys as fl32(v)).  Up to int(beta * K) clients sending anything,
                 NaN and inf included, cannot move a coordinate outside the
                 range of the honest values.
 
@@ -299,6 +300,43 @@ def trimmed_mean_rows(d_ptrs: torch.Tensor, K: int, N: int, trim: int, out: torc
                                             flags, nat.stream_handle()), "trimmed_mean")
 
 
+# fedagg_trimmed_mean_wide holds up to 1024 clients (csrc/trimmed_wide.hip)
+TRIMMED_WIDE_MAX_CLIENTS = nat.TRIMMED_WIDE_MAX_CLIENTS
+# The K tiers of the wide kernel (K <= tier) that coordinate_wise_trimmed_mean
+# hands to it above 128 clients: those where its median time beat
+# trimmed_mean_rows_torch's by more than the larger min-max spread of the two
+# (GEOMED_AUTO_FUSED's rule; tools/trimmed_wide_probe.py ->
+# profiles/trimmed_wide_probe.json, NOTES.md §5b); a tier that did not win
+# takes the torch path.  Measured at 4,194,304 columns, kernel and torch path
+# launched alternately on the same rows, median of 10, torch / kernel (fp32,
+# bf16; K = the full tier, then a padded K); spreads under 0.24 ms for the
+# kernel and under 70 ms for the torch path:
+#   tier  256: 63.1x, 63.4x (K = 256: 1.40 ms against 88 ms); 53.4x, 44.0x (K = 200)
+#   tier  512: 50.8x, 52.5x (K = 512: 4.03 ms against 205 ms); 40.1x, 37.6x (K = 384)
+#   tier 1024: 43.8x, 47.1x (K = 1024: 11.8 ms against 516 ms); 34.3x, 34.3x (K = 700)
+TRIMMED_WIDE_AUTO = {256: True, 512: True, 1024: True}
+
+
+def trimmed_wide_auto(K: int) -> bool:
+    """Whether coordinate_wise_trimmed_mean runs the wide kernel for K clients
+    above TRIMMED_MAX_CLIENTS (TRIMMED_WIDE_AUTO)."""
+    if K > TRIMMED_WIDE_MAX_CLIENTS:
+        return False
+    return TRIMMED_WIDE_AUTO[min(t for t in TRIMMED_WIDE_AUTO if K <= t)]
+
+
+def trimmed_mean_rows_wide(d_ptrs: torch.Tensor, K: int, N: int, trim: int, out: torch.Tensor) -> None:
+    """Coordinate-wise trimmed mean of K <= 1024 device rows of out's dtype
+    (fp32, bf16 or f16; fedagg_trimmed_mean_wide): trimmed_mean_rows's
+    operation, bit for bit, with the column spread over 4 or 8 lanes.  One
+    kernel form for every alignment."""
+    kn._require_cuda(out, "trimmed_mean_wide")
+    if out.dtype not in _MEDIAN_DT:
+        raise TypeError(f"trimmed_mean_wide: fp32, bf16 or f16 rows (got {out.dtype})")
+    nat.check(nat.lib().fedagg_trimmed_mean_wide(_MEDIAN_DT[out.dtype], d_ptrs.data_ptr(), K, N, trim,
+                                                 out.data_ptr(), 0, nat.stream_handle()), "trimmed_mean_wide")
+
+
 def _order_keys(x: torch.Tensor) -> torch.Tensor:
     """int32 keys of fp32 values whose integer order is the kernels' total
     order (-inf < negatives < -0 < +0 < positives < +inf < every NaN).  The
@@ -363,8 +401,10 @@ def coordinate_wise_trimmed_mean(raw_client_grad_list: List[Tuple[float, "Ordere
     """The coordinate-wise trimmed mean of Yin et al. over the clients' dicts:
     every coordinate of EVERY key (BatchNorm statistics and counters too)
     drops its int(beta * K) smallest and largest client values and averages
-    the rest (fedagg_trimmed_mean; trimmed_mean_rows_torch above 128
-    clients).  Sample counts are ignored, as by the median.  Returns a new
+    the rest: fedagg_trimmed_mean up to 128 clients, fedagg_trimmed_mean_wide
+    from 129 to 1024 (in the tiers of TRIMMED_WIDE_AUTO), for the float keys'
+    row and the fp32 row of the integer keys alike, and
+    trimmed_mean_rows_torch above that; the three agree bit for bit.  Sample counts are ignored, as by the median.  Returns a new
     OrderedDict in client 0's key order, on the inputs' device; integer keys
     come back fp32, as FedMLAggOperator.agg returns them.  No client dict is
     modified."""
@@ -397,6 +437,9 @@ def coordinate_wise_trimmed_mean(raw_client_grad_list: List[Tuple[float, "Ordere
                 if K <= TRIMMED_MAX_CLIENTS:
                     row = torch.empty(g.padded, dtype=g.dtype, device=dev)
                     trimmed_mean_rows(g.d_ptrs, K, g.length, trim, row, aligned=True)
+                elif trimmed_wide_auto(K):
+                    row = torch.empty(g.padded, dtype=g.dtype, device=dev)
+                    trimmed_mean_rows_wide(g.d_ptrs, K, g.length, trim, row)
                 else:
                     row = trimmed_mean_rows_torch(g.rows[:, :g.length], trim)
                 yield g, row

@@ -373,11 +373,33 @@ int fedagg_median(int32_t dtype, const void* const* d_src, int32_t K,
  * unpruned pairwise network (K tiers 8 .. 128, launches of 2^30 columns), for
  * every alignment; flags is reserved.  FEDAGG_EINVAL for K < 1, N < 0,
  * trim < 0, 2 * trim >= K, a null pointer or another dtype; FEDAGG_ENOKERNEL
- * for K > FEDAGG_TRIMMED_MAX_CLIENTS (callers sort in torch ops above it). */
+ * for K > FEDAGG_TRIMMED_MAX_CLIENTS (fedagg_trimmed_mean_wide holds up to
+ * FEDAGG_TRIMMED_WIDE_MAX_CLIENTS; callers sort in torch ops above that). */
 #define FEDAGG_TRIMMED_MAX_CLIENTS 128
 int fedagg_trimmed_mean(int32_t dtype, const void* const* d_src, int32_t K,
                         int64_t N, int32_t trim, void* d_out, uint32_t flags,
                         fedagg_stream_t stream);
+
+/* The coordinate-wise trimmed mean for up to 1024 clients
+ * (csrc/trimmed_wide.hip).  The specification is steps 1-5 of
+ * fedagg_trimmed_mean above, by reference: the same order, kept ranks,
+ * sequential fp32 chain from s[trim], IEEE division, single rounding of 16-bit
+ * rows and NaN rule, so the result is bit-identical to fedagg_trimmed_mean's
+ * wherever both take K (a NaN's payload aside).  Accepts 1 <= K <=
+ * FEDAGG_TRIMMED_WIDE_MAX_CLIENTS; K below 129 runs padded in the first tier.
+ * P adjacent lanes hold a column, R values each, sorted in registers and
+ * merged across the lanes (4 x 64 up to 256 clients, 4 x 128 up to 512,
+ * 8 x 128 up to 1024); the chain then runs lane after lane.  One launch, for
+ * every alignment; stream-ordered, allocates nothing, does not synchronise;
+ * flags is reserved.  Checked before any HIP call: FEDAGG_EINVAL for K < 1,
+ * N < 0, trim < 0, 2 * trim >= K, a null pointer, another dtype or N beyond
+ * 2^31 - 1 blocks (of 64 columns up to 512 clients, 32 above);
+ * FEDAGG_ENOKERNEL for K > FEDAGG_TRIMMED_WIDE_MAX_CLIENTS.  N == 0 is
+ * FEDAGG_OK. */
+#define FEDAGG_TRIMMED_WIDE_MAX_CLIENTS 1024
+int fedagg_trimmed_mean_wide(int32_t dtype, const void* const* d_src, int32_t K,
+                             int64_t N, int32_t trim, void* d_out,
+                             uint32_t flags, fedagg_stream_t stream);
 
 /* Mean of the values nearest the median: stage 2 of the "wise_bulyan" defense
  * (Bulyan, El Mhamdi et al.; csrc/nearmedian.hip) over K fp32 rows, K being
