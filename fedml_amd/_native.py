@@ -30,6 +30,7 @@ TRIMMED_MAX_CLIENTS = 128  # FEDAGG_TRIMMED_MAX_CLIENTS
 TRIMMED_WIDE_MAX_CLIENTS = 1024  # FEDAGG_TRIMMED_WIDE_MAX_CLIENTS
 GEOMED_MAX_CLIENTS = 128  # FEDAGG_GEOMED_MAX_CLIENTS
 NEARMEDIAN_MAX_CLIENTS = 128  # FEDAGG_NEARMEDIAN_MAX_CLIENTS
+NEARMEDIAN_WIDE_MAX_CLIENTS = 1024  # FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS
 # FEDAGG_FEDOPT_*: the launch kinds of fedagg_wsum_fedopt_batch (besides the FEDAGG_OPT_* codes)
 FEDOPT_AVG, FEDOPT_SGD, FEDOPT_ADAM, FEDOPT_ADAMW, FEDOPT_ADAGRAD, FEDOPT_RMSPROP = 0, 16, 17, 18, 19, 20
 
@@ -85,6 +86,7 @@ SIGNATURES = {
     "fedagg_trimmed_mean": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_trimmed_mean_wide": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_nearmedian_mean_f32": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _U32, _P]),
+    "fedagg_nearmedian_mean_wide_f32": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_sum_mod_i64": (ctypes.c_int, [_P, _I32, _I64, _I64, _P, _U32, _P]),
     "fedagg_lsa_reconstruct_f32": (ctypes.c_int, [_P, _I32, _I64, _P, _I64, _I32, _F, _P, _U32, _P]),
     "fedagg_host_pack": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32]),

@@ -18,7 +18,8 @@ SRC = os.path.join(HERE, "csrc", "fedagg.hip")
 # unchanged unit is not recompiled), then linked
 SRCS = [SRC, os.path.join(HERE, "csrc", "robust.hip"), os.path.join(HERE, "csrc", "median.hip"),
         os.path.join(HERE, "csrc", "trimmed.hip"), os.path.join(HERE, "csrc", "geomed.hip"),
-        os.path.join(HERE, "csrc", "nearmedian.hip"), os.path.join(HERE, "csrc", "trimmed_wide.hip")]
+        os.path.join(HERE, "csrc", "nearmedian.hip"), os.path.join(HERE, "csrc", "trimmed_wide.hip"),
+        os.path.join(HERE, "csrc", "nearmedian_wide.hip")]
 # headers under csrc/ that the units share: a change rebuilds every unit
 CSRC_HEADERS = [os.path.join(HERE, "csrc", "sortnet.h"), os.path.join(HERE, "csrc", "lanesort.h"),
                 os.path.join(HERE, "csrc", "host_util.h")]

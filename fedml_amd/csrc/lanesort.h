@@ -4,8 +4,9 @@
 // network (sortnet.h); the sorted runs are then merged across lanes by reverse
 // pairing plus half-cleaner stages (single DPP movs and v_med3 against ±inf),
 // one level per doubling of the lane group.  median.hip describes the scheme
-// where it prunes the last level (median_lanes_kernel); trimmed_wide.hip runs
-// every level.  Everything is internal to the including translation unit.
+// where it prunes the last level (median_lanes_kernel); trimmed_wide.hip and
+// nearmedian_wide.hip run every level.  Everything is internal to the
+// including translation unit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,6 +57,17 @@ __device__ __forceinline__ float xor_mov(float x) {
   if constexpr (dpp_xor_ok<M>()) return dpp_mov<dpp_xor_ctrl<M>()>(x);
   else if constexpr (M == 4) return dpp_mov<dpp_xor_ctrl<3>()>(dpp_mov<dpp_xor_ctrl<7>()>(x));  // (i ^ 7) ^ 3
   else return __int_as_float(__shfl_xor(__float_as_int(x), M, 64));
+}
+
+// sum of x over the P adjacent lanes of a column (every lane gets it)
+template <int P>
+__device__ __forceinline__ int lanes_count_sum(int x) {
+  static_assert(P <= 16, "a lane group inside one DPP row");
+  if constexpr (P >= 2) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<1>(), 0xF, 0xF, true);
+  if constexpr (P >= 4) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<2>(), 0xF, 0xF, true);
+  if constexpr (P >= 8) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<7>(), 0xF, 0xF, true);  // the other quad's sum
+  if constexpr (P >= 16) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<15>(), 0xF, 0xF, true);  // the other half's
+  return x;
 }
 
 // min (lower lanes, sel = -inf) or max (upper lanes, sel = +inf) of own

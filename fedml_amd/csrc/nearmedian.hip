@@ -72,9 +72,7 @@ __device__ __forceinline__ void shift_stages(float (&a)[KMAX], int keep) {
   if constexpr (SH > 1) shift_stages<KMAX, NB, SH / 2>(a, keep);
 }
 
-// d(x): x - m is NaN only for equal infinities, which fmaxf turns into the 0
-// of x == m; every other x == m gives 0 by itself
-__device__ __forceinline__ float near_dist(float x, float m) { return fmaxf(__builtin_fabsf(x - m), 0.f); }
+// d(x) is near_dist (sortnet.h, shared with nearmedian_wide.hip)
 
 template <int KMAX, int J>
 __device__ __forceinline__ void count_slot(const float (&v)[KMAX], const float (&a)[KMAX], float m, int lo_min,

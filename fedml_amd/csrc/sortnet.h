@@ -2,9 +2,9 @@
 // compile-time pairwise sorting network, the element types (fp32, bf16, f16
 // as fp32 "selection values"), the per-slot row load (load_slot) and, on the
 // host, the chunked launch (launch_col_chunks) and the tier ladder (with_tier).
-// Included by median.hip, trimmed.hip, trimmed_wide.hip and nearmedian.hip
-// (and by lanesort.h, the lane-group sort above 128 clients); everything is
-// internal to the including translation unit.
+// Included by median.hip, trimmed.hip, trimmed_wide.hip, nearmedian.hip and
+// nearmedian_wide.hip (and by lanesort.h, the lane-group sort above 128
+// clients); everything is internal to the including translation unit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -222,6 +222,12 @@ template <class E>
 constexpr typename E::S trim_pos_inf() {
   return __builtin_bit_cast(typename E::S, static_cast<raw_bits_t<E>>(E::kPosInf));
 }
+
+// The nearest-to-median kernels (nearmedian.hip, nearmedian_wide.hip): the
+// distance d(x) of a sorted value from the median m.  x - m is NaN only for
+// equal infinities, which fmaxf turns into the 0 of x == m; every other
+// x == m gives 0 by itself
+__device__ __forceinline__ float near_dist(float x, float m) { return fmaxf(__builtin_fabsf(x - m), 0.f); }
 
 // Row base of client row p for a launch starting at column col0 (> 0 only
 // past 2^30 columns): an opaque SGPR pair, so the loads keep the

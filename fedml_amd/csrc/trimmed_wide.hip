@@ -41,16 +41,7 @@ namespace {
 template <class E>
 __device__ typename E::S g_trimmed_wide_pad = trim_pos_inf<E>();
 
-// sum of x over the P adjacent lanes of a column (every lane gets it)
-template <int P>
-__device__ __forceinline__ int lanes_count_sum(int x) {
-  static_assert(P <= 16, "a lane group inside one DPP row");
-  if constexpr (P >= 2) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<1>(), 0xF, 0xF, true);
-  if constexpr (P >= 4) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<2>(), 0xF, 0xF, true);
-  if constexpr (P >= 8) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<7>(), 0xF, 0xF, true);  // the other quad's sum
-  if constexpr (P >= 16) x += __builtin_amdgcn_mov_dpp(x, dpp_xor_ctrl<15>(), 0xF, 0xF, true);  // the other half's
-  return x;
-}
+// lanes_count_sum: lanesort.h (shared with nearmedian_wide.hip)
 
 template <int P, int R, bool FULL, class E, int BS = 256>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void trimmed_mean_lanes_kernel(

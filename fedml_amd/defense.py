@@ -57,8 +57,10 @@ that are pure reductions over the client axis.
                 2 averages, per coordinate of EVERY key, the beta = theta - 2f
                 selected values nearest the coordinate's median
                 (fedagg_nearmedian_mean_f32, specified in include/fedagg.h:
-                one launch over the whole row up to 128 selected clients, the
-                same rule in torch ops above that).  K >= 4f + 3.
+                one launch over the whole row up to 128 selected clients,
+                fedagg_nearmedian_mean_wide_f32 from 129 to 1024 in the tiers
+                of NEARMEDIAN_WIDE_AUTO, the same rule in torch ops above
+                that).  K >= 4f + 3.
 
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
@@ -1175,9 +1177,47 @@ def nearmedian_mean_rows(d_ptrs: torch.Tensor, K: int, N: int, keep: int, out: t
                                                    nat.stream_handle()), "nearmedian_mean")
 
 
+# fedagg_nearmedian_mean_wide_f32 holds up to 1024 rows (csrc/nearmedian_wide.hip)
+NEARMEDIAN_WIDE_MAX_CLIENTS = nat.NEARMEDIAN_WIDE_MAX_CLIENTS
+# The tiers of the wide kernel (theta <= tier) that bulyan hands to it above
+# 128 selected clients, by TRIMMED_WIDE_AUTO's rule: those where its median
+# time beat nearmedian_mean_rows_torch's by more than the larger min-max spread
+# of the two (tools/nearmedian_wide_probe.py ->
+# profiles/nearmedian_wide_probe.json, NOTES.md §5b); a tier that did not win
+# takes the torch path.  Measured at 4,194,304 fp32 columns, kernel and torch
+# path launched alternately on the same rows, median of 10, torch / kernel at
+# keep = K - 2 (K // 8) and at keep = K (K = the full tier, then a padded K);
+# spreads under 0.31 ms for the kernel and under 310 ms for the torch path,
+# which is 111 ms to 2.4 s slower:
+#   tier  256: 78.3x, 83.1x (K = 256: 1.87 ms against 147 ms); 61.5x, 64.0x (K = 200)
+#   tier  512: 86.4x, 107.0x (K = 512: 4.74 ms against 410 ms); 58.8x, 70.9x (K = 384)
+#   tier 1024: 107.8x, 176.1x (K = 1024: 13.4 ms against 1.44 s); 68.7x, 78.3x (K = 700)
+NEARMEDIAN_WIDE_AUTO = {256: True, 512: True, 1024: True}
+
+
+def nearmedian_wide_auto(theta: int) -> bool:
+    """Whether bulyan runs the wide kernel for theta selected clients above
+    NEARMEDIAN_MAX_CLIENTS (NEARMEDIAN_WIDE_AUTO)."""
+    if theta > NEARMEDIAN_WIDE_MAX_CLIENTS:
+        return False
+    return NEARMEDIAN_WIDE_AUTO[min(t for t in NEARMEDIAN_WIDE_AUTO if theta <= t)]
+
+
+def nearmedian_mean_rows_wide(d_ptrs: torch.Tensor, K: int, N: int, keep: int, out: torch.Tensor) -> None:
+    """nearmedian_mean_rows's operation, bit for bit, for K <= 1024 fp32 device
+    rows (fedagg_nearmedian_mean_wide_f32): the column spread over 4 or 8
+    lanes.  One kernel form for every alignment."""
+    kn._require_cuda(out, "nearmedian_mean_wide")
+    if out.dtype != torch.float32:
+        raise TypeError(f"nearmedian_mean_wide: fp32 rows (got {out.dtype})")
+    nat.check(nat.lib().fedagg_nearmedian_mean_wide_f32(d_ptrs.data_ptr(), K, N, keep, out.data_ptr(), 0,
+                                                        nat.stream_handle()), "nearmedian_mean_wide")
+
+
 def nearmedian_mean_rows_torch(rows, keep: int, chunk_cols: "int | None" = None) -> torch.Tensor:
     """The specification of fedagg_nearmedian_mean_f32 in torch ops, on any
-    device and for any K: the slow path above 128 selected rows.  rows: a
+    device and for any K: the slow path above 128 selected rows where the wide
+    kernel does not run.  rows: a
     (K, N) fp32 tensor or a list of K fp32 rows of N elements.  Per column
     chunk the order keys are sorted and mapped back to values; with NaN
     standing as +inf the window start is lo_min plus the number of j in
@@ -1228,6 +1268,14 @@ def nearmedian_mean_rows_torch(rows, keep: int, chunk_cols: "int | None" = None)
     return out
 
 
+# bulyan_select sorts every row of the distances once above this many clients;
+# up to it the n x n sub-matrix is re-sorted in every round, which is as fast
+# there (NOTES.md, "Bulyan above 128 selected clients")
+BULYAN_PRESORT_ABOVE = 256
+# rounds between two compactions of the presorted rows
+_BULYAN_COMPACT_EVERY = 32
+
+
 def bulyan_select(D, f: int):
     """Stage 1 of Bulyan on the host: theta = K - 2f clients by repeated Krum
     over the K x K squared distances D (computed once; every round re-scores
@@ -1250,6 +1298,8 @@ def bulyan_select(D, f: int):
     theta = K - 2 * f
     if theta < 1:
         raise ValueError(f"bulyan: K = {K} clients leave no selection at f = {f}")
+    if K > BULYAN_PRESORT_ABOVE:
+        return _bulyan_select_presorted(D, f, theta)
     R = list(range(K))
     selected, scores = [], []
     for _ in range(theta):
@@ -1269,6 +1319,95 @@ def bulyan_select(D, f: int):
         scores.append(float(sc[p]))
         del R[p]
     return selected, scores
+
+
+def _bulyan_select_presorted(D: np.ndarray, f: int, theta: int):
+    """bulyan_select's rounds without the sort per round, bit for bit.  Every
+    row of D is sorted once, NaN last and without the client itself, and kept
+    as a COLUMN of `vals` (vals[j][i]: client i's j-th nearest), with the
+    neighbour it belongs to in `ids`.  A round masks the entries of the client
+    it removed to +0.0 and forms every score as the sequential sum down the
+    columns, one vector add per sorted position (np.cumsum along a row is one
+    dependent add after the other; down the columns the clients go side by
+    side).  Adding +0.0 leaves a non-negative, infinite or NaN partial sum as
+    it is, so a column's sum up to its c-th live entry is the sum of its c
+    smallest live distances in ascending order; equal distances give equal
+    sums in whichever order they stand.  The c-th live entry of column i is at
+    at[i] = c - 1 + (masked entries at or before it), found from the masked
+    positions since the last compaction; the rows up to the lowest at are
+    added whole, the few up to the highest under at >= j.  Every
+    _BULYAN_COMPACT_EVERY rounds the masked entries and the removed clients'
+    columns are dropped, so at most that many rows are ragged."""
+    K = len(D)
+    order = np.argsort(D, axis=1, kind="stable")  # NaN last, as np.sort places it
+    ids = order[order != np.arange(K)[:, None]].reshape(K, K - 1)  # the client itself is no neighbour
+    vals = np.ascontiguousarray(np.take_along_axis(D, ids, axis=1).T)
+    ids = np.ascontiguousarray(ids.T)
+    cols = np.arange(K)  # the client of every column
+    alive = np.ones(K, dtype=bool)
+    where, gone = _bulyan_positions(ids), []
+    selected, scores = [], []
+    for _ in range(theta):
+        if len(gone) >= _BULYAN_COMPACT_EVERY:
+            vals, ids, cols = _bulyan_compact(vals, ids, cols, alive)
+            alive = np.ones(len(cols), dtype=bool)
+            where, gone = _bulyan_positions(ids), []
+        R = np.flatnonzero(alive)
+        n = len(R)
+        c = min(max(1, n - f - 2), n - 1)
+        if c < 1:  # a single client left: nothing to sum
+            sc = np.zeros(n)
+        else:
+            # the least x with x + 1 - (masked entries at or before x) = c, from below
+            at = np.full(len(cols), c - 1)
+            if gone:
+                masked = np.stack(gone)
+                while True:
+                    nxt = c - 1 + (masked <= at).sum(axis=0)
+                    if np.array_equal(nxt, at):
+                        break
+                    at = nxt
+            lo, hi = int(at[R].min()), int(at[R].max())  # a live column holds n - 1 >= c live entries
+            with np.errstate(invalid="ignore", over="ignore"):
+                acc = vals[0].copy()  # the chain starts from the value: 0.0 + v is v for every v a distance can be
+                for j in range(1, lo + 1):
+                    np.add(acc, vals[j], out=acc)
+                for j in range(lo + 1, hi + 1):
+                    np.add(acc, np.where(at >= j, vals[j], 0.0), out=acc)
+            sc = acc[R]
+        sc = np.where(np.isnan(sc), np.inf, sc)
+        p = int(np.argmin(sc))  # the first of equal scores: R is ascending, and so is cols
+        g = int(R[p])
+        selected.append(int(cols[g]))
+        scores.append(float(sc[p]))
+        alive[g] = False
+        at_g = where[:, g]  # where the removed client stands in every column (its own: nowhere)
+        has = at_g < len(vals)
+        vals[at_g[has], np.flatnonzero(has)] = 0.0  # a NaN distance to it becomes +0.0 too
+        gone.append(at_g)
+    return selected, scores
+
+
+def _bulyan_positions(ids: np.ndarray) -> np.ndarray:
+    """where[i][g]: the row at which client g stands in column i of ids
+    ((m, w): m sorted positions of w clients); m for the client itself."""
+    m, w = ids.shape
+    where = np.full((w, w), m, dtype=np.intp)
+    np.put_along_axis(where, np.ascontiguousarray(ids.T), np.arange(m)[None, :], axis=1)
+    return where
+
+
+def _bulyan_compact(vals: np.ndarray, ids: np.ndarray, cols: np.ndarray, alive: np.ndarray):
+    """vals, ids and cols without the removed clients: their columns, and their
+    (masked) entry in every other column; ids renumbered to the new columns."""
+    R = np.flatnonzero(alive)
+    n = len(R)
+    sub = np.ascontiguousarray(ids[:, R].T)
+    live = alive[sub]
+    renumber = np.cumsum(alive) - 1
+    new_ids = renumber[sub[live].reshape(n, n - 1)]
+    new_vals = np.ascontiguousarray(vals[:, R].T)[live].reshape(n, n - 1)
+    return np.ascontiguousarray(new_vals.T), np.ascontiguousarray(new_ids.T), cols[R]
 
 
 class BulyanInfo:
@@ -1298,8 +1437,9 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
     EVERY key (BatchNorm statistics and counters too, as wise_trimmed_mean)
     the mean of the beta = theta - 2f selected values nearest the coordinate's
     median: one fedagg_nearmedian_mean_f32 launch over the whole row through a
-    pointer table of the selected rows (nearmedian_mean_rows_torch above 128
-    selected clients).
+    pointer table of the selected rows, fedagg_nearmedian_mean_wide_f32 from
+    129 to 1024 selected clients (in the tiers of NEARMEDIAN_WIDE_AUTO) and
+    nearmedian_mean_rows_torch for the rest.
 
     fp32 models (integer buffers allowed, entering as fl32(v)).  Sample counts
     are ignored, as by the median.  Returns a new OrderedDict in client 0's
@@ -1332,11 +1472,14 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
             chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
             D = pairdist2_rows(g.d_ptrs, K, chunks, n_chunks, dev, method).cpu().numpy()
             selected, scores = bulyan_select(D, f)
-        if theta <= NEARMEDIAN_MAX_CLIENTS:
+        if theta <= NEARMEDIAN_MAX_CLIENTS or nearmedian_wide_auto(theta):
             ptrs = g.d_ptrs if selected == list(range(K)) else \
                 kn.upload_i64([g.rows[i].data_ptr() for i in selected], dev)
             row = torch.zeros(g.padded, dtype=torch.float32, device=dev)
-            nearmedian_mean_rows(ptrs, theta, g.length, beta, row)
+            if theta <= NEARMEDIAN_MAX_CLIENTS:
+                nearmedian_mean_rows(ptrs, theta, g.length, beta, row)
+            else:
+                nearmedian_mean_rows_wide(ptrs, theta, g.length, beta, row)
         else:
             row = nearmedian_mean_rows_torch([g.rows[i][:g.length] for i in selected], beta)
         out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)

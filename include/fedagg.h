@@ -444,6 +444,29 @@ int fedagg_nearmedian_mean_f32(const float* const* d_src, int32_t K, int64_t N,
                                int32_t keep, float* d_out, uint32_t flags,
                                fedagg_stream_t stream);
 
+/* The mean of the values nearest the median for up to 1024 rows
+ * (csrc/nearmedian_wide.hip).  The specification is steps 1-6 of
+ * fedagg_nearmedian_mean_f32 above, by reference: the same order, median
+ * rank, distance, window with its tie rule, sequential fp32 chain from s[lo],
+ * IEEE division and NaN rule, so the result is bit-identical to
+ * fedagg_nearmedian_mean_f32's wherever both take K (a NaN's payload aside).
+ * Accepts 1 <= K <= FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS; K below 129 runs
+ * padded in the first tier.  fedagg_trimmed_mean_wide's form: P adjacent
+ * lanes hold a column, R values each, sorted in registers and merged across
+ * the lanes (4 x 64 up to 256 rows, 4 x 128 up to 512, 8 x 128 up to 1024);
+ * the values `keep` ranks above reach their partners through LDS, and the
+ * chain then runs lane after lane.  fp32 only, one launch, for every
+ * alignment; stream-ordered, allocates nothing, does not synchronise; flags
+ * is reserved.  Checked before any HIP call: FEDAGG_EINVAL for K < 1, N < 0,
+ * keep < 1, keep > K, a null pointer or N beyond 2^31 - 1 blocks (of 64
+ * columns up to 512 rows, 32 above); FEDAGG_ENOKERNEL for K >
+ * FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS.  N == 0 is FEDAGG_OK without a
+ * launch. */
+#define FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS 1024
+int fedagg_nearmedian_mean_wide_f32(const float* const* d_src, int32_t K,
+                                    int64_t N, int32_t keep, float* d_out,
+                                    uint32_t flags, fedagg_stream_t stream);
+
 /* Distance-based defenses (csrc/robust.hip).  Rows are K fp32 device
  * pointers; the columns that count (FedML's vectorize_weight: every key but
  * BatchNorm running stats and counters, core/security/common/utils.py:8-21)
