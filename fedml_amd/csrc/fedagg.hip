@@ -730,6 +730,7 @@ struct LsaEpi {
   const int64_t* mask;
   float* out;
   int64_t p;
+  double half;       // fl64((p-1)/2), rounded once from the exact quotient as Python's (p - 1) / 2 is
   double inv_scale;  // 2^-q (exact)
   float w;
   static constexpr int E = 2;
@@ -741,7 +742,7 @@ struct LsaEpi {
     const int64_t m = floor_mod(wrap_add(acc, -mk), p);
     // flag = X_q - (p-1)/2 > 0, computed by numpy in float64
     const double xq = static_cast<double>(m);
-    const double v = (xq - (static_cast<double>(p) - 1.0) / 2.0 > 0.0) ? xq - static_cast<double>(p) : xq;
+    const double v = (xq - half > 0.0) ? xq - static_cast<double>(p) : xq;
     const float f = static_cast<float>(v * inv_scale);  // exact scale, then RNE to fp32
     return f * w;
   }
@@ -2511,7 +2512,9 @@ int fedagg_lsa_reconstruct_f32(const int64_t* const* d_src, int32_t K, int64_t N
   if (!d_src || !d_mask || !d_out) return set_error(FEDAGG_EINVAL, "fedagg_lsa_reconstruct_f32: null pointer");
   if (N == 0) return FEDAGG_OK;
   Seg<OpWrapSumI64> s{d_src, N};
-  LsaEpi epi{d_mask, d_out, p, ldexp(1.0, -q_bits), w};
+  // p - 1 converts with one rounding and the halving is exact, so this is the correctly rounded (p-1)/2;
+  // (double(p) - 1.0) / 2.0 rounds twice and lands one ulp off for some p above 2^53.
+  LsaEpi epi{d_mask, d_out, p, static_cast<double>(p - 1) / 2.0, ldexp(1.0, -q_bits), w};
   return launch_epi<OpWrapSumI64>(s, epi, ConstW<int64_t>{0}, K, (flags & FEDAGG_ALIGNED16) != 0,
                                   reinterpret_cast<hipStream_t>(stream), "fedagg_lsa_reconstruct_f32");
 }

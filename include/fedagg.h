@@ -589,7 +589,9 @@ int fedagg_wsum_rlr_f32(const float* const* d_src, const float* d_w, int32_t K,
  * LightSecAggAggregator.aggregate_model_reconstruction
  * (cross_silo/lightsecagg/lsa_fedml_aggregator.py:139-166) with
  * transform_finite_to_tensor / my_q_inv (lightsecagg.py:157-182):
- *   m = (Σ_i x_i − mask) mod p;  v = m > (p−1)/2 ? m − p : m  (float64);
+ *   m = (Σ_i x_i − mask) mod p;  v = fl64(m) − h > 0 ? fl64(m) − fl64(p) : fl64(m)
+ *   with h = fl64((p−1)/2), the exact quotient rounded once (Python's
+ *   (p − 1) / 2; for p > 2^53 not what (double(p) − 1) / 2 gives);
  *   out = fl32( fl32(v / 2^q_bits) · w )   with w = fl32(1 / K_active).
  * d_mask is the decoded aggregate mask laid out like the client rows. */
 int fedagg_sum_mod_i64(const int64_t* const* d_src, int32_t K, int64_t N,
