@@ -1,12 +1,14 @@
-// lanesort.h — the lane-group sort that the kernels above 128 clients share:
-// P adjacent lanes hold one column, each R of its P·R values in registers
-// (slot s = sub·R + j).  Every lane sorts its R values with the pairwise
-// network (sortnet.h); the sorted runs are then merged across lanes by reverse
-// pairing plus half-cleaner stages (single DPP movs and v_med3 against ±inf),
-// one level per doubling of the lane group.  median.hip describes the scheme
-// where it prunes the last level (median_lanes_kernel); trimmed_wide.hip and
-// nearmedian_wide.hip run every level.  Everything is internal to the
-// including translation unit.
+// lanesort.h — what the lane-group kernels above 128 clients share: P adjacent
+// lanes hold one column, each R of its P·R values in registers (slot
+// s = sub·R + j), their addresses in the block's LDS slot table
+// (lanes_slot_ptr).  Every lane sorts its R values with the pairwise network
+// (sortnet.h); the sorted runs are then merged across lanes by reverse pairing
+// plus half-cleaner stages (single DPP movs and v_med3 against ±inf), one level
+// per doubling of the lane group.  median.hip describes the scheme where it
+// prunes the last level (median_lanes_kernel); trimmed_wide.hip and
+// nearmedian_wide.hip run every level (lanes_sort_all).  On the host: the
+// launch (launch_lanes) and the tiers of 129 to 1024 clients (with_lane_tier).
+// Everything is internal to the including translation unit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,6 +32,18 @@ __device__ __forceinline__ T lanes_load(const T __attribute__((address_space(1))
     return __builtin_nontemporal_load(p);
   else
     return *p;
+}
+
+// Address of slot j of lane `sub`, as a T, at byte offset boff of the rows (a
+// padded slot: of its constant).  The table is skewed by kLanesSkew entries per
+// lane group (median_lanes_kernel, which stages it, says why).
+constexpr int kLanesSkew = 2;
+template <int R, bool FULL, class T, class S>
+__device__ __forceinline__ const T __attribute__((address_space(1)))* lanes_slot_ptr(
+    const S* const* rows, const uint64_t* offmask, int sub, int j, uint64_t boff) {
+  const int q = sub * (R + kLanesSkew) + j;
+  const uint64_t off = FULL ? boff : (boff & offmask[q]);
+  return as_global(reinterpret_cast<const T*>(reinterpret_cast<const char*>(rows[q]) + off));
 }
 
 template <int CTRL>
@@ -119,6 +133,37 @@ __device__ __forceinline__ void lanes_merge_levels(float (&v)[R], int sub) {
     lane_bitonic_merge(v);
     lanes_merge_levels<G * 2, P, R>(v, sub);
   }
+}
+
+// the in-lane network, then every merge level (G = P included): slot s holds rank s
+template <int P, int R>
+__device__ __forceinline__ void lanes_sort_all(float (&v)[R], int sub) {
+  pairwise_sort<R>(v);
+  lanes_merge_levels<2, 2 * P, R>(v, sub);
+}
+
+// Host side.  One launch over N columns, P lanes per column in blocks of BS:
+// kernel(src, K, N, mid..., out), `full` when K is the tier's P·R, else `padded`.
+// A grid past 2^31 - 1 blocks is "<what>: N too large".  As in launch_col_chunks
+// the kernel's own arguments follow `out` here: a pack is deduced only at the end.
+template <class Kern, class S, class... Mid>
+int launch_lanes(const char* what, Kern full, Kern padded, bool is_full, int P, int BS, hipStream_t st,
+                 const S* const* src, int K, int64_t N, S* out, Mid... mid) {
+  if (N > int64_t(0x7fffffff) * BS / P) return set_error(FEDAGG_EINVAL, std::string(what) + ": N too large");
+  const unsigned grid = unsigned((N * P + BS - 1) / BS);
+  const Kern kernel = is_full ? full : padded;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(BS), 0, st, src, K, N, mid..., out);
+  return check_launch(what);
+}
+
+// The tiers of 129 to 1024 clients (the callers bound K): f(P, R) as
+// std::integral_constant<int, ..> values.  Each tier's call stands before the
+// next tier's (with_tier, sortnet.h: the order the kernels are emitted in).
+template <class F>
+int with_lane_tier(int K, F f) {
+  if (K <= 256) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 64>{});
+  if (K <= 512) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 128>{});
+  return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 128>{});
 }
 
 }  // namespace

@@ -331,7 +331,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void me
   using S = typename E::S;
   static_assert(P == 2 || P == 4 || P == 8 || P == 16 || P == 32, "2 to 32 lanes per column");
   static_assert(R == 64 || R == 128, "64 or 128 values per lane");
-  constexpr int KMAX = P * R, PAD = 2;
+  constexpr int KMAX = P * R, PAD = kLanesSkew;
   // Row pointer of every slot, skewed by PAD entries per lane group so the P
   // lanes of a column read different LDS banks.  A padded slot (K < KMAX)
   // points at a ±inf constant and its column offset is masked to 0, so the
@@ -361,10 +361,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void me
 #pragma unroll
   for (int j = 0; j < R; ++j) {
     if (j % 16 == 0 && j) __builtin_amdgcn_sched_barrier(0);
-    const int q = sub * (R + PAD) + j;
-    const uint64_t off = FULL ? boff : (boff & offmask[q]);
-    const auto row = reinterpret_cast<const char*>(rows[q]);
-    v[j] = E::widen(lanes_load(as_global(reinterpret_cast<const S*>(row + off))));
+    v[j] = E::widen(lanes_load(lanes_slot_ptr<R, FULL, S>(rows, offmask, sub, j, boff)));
   }
   __builtin_amdgcn_sched_barrier(0);  // every load in flight before the first test (see median_kernel)
 #pragma unroll
@@ -378,9 +375,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void me
     // re-read this lane's slots in client order (cache hits; see median_kernel)
 #pragma unroll 1
     for (int j = 0; j < R; ++j) {
-      const int q = sub * (R + PAD) + j;
-      const uint64_t off = FULL ? boff : (boff & offmask[q]);
-      const S r = *as_global(reinterpret_cast<const S*>(reinterpret_cast<const char*>(rows[q]) + off));
+      const S r = *lanes_slot_ptr<R, FULL, S>(rows, offmask, sub, j, boff);
       if (E::raw_nan(r)) {
         nan_slot = sub * R + j;
         nan_raw = r;
@@ -416,15 +411,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void me
 
 template <int P, int R, class E = MedF32, int BS = 256>
 int launch_median_lanes(const typename E::S* const* src, int K, int64_t N, typename E::S* out, hipStream_t st) {
-  const int64_t grid = (N * P + BS - 1) / BS;
-  if (grid > 0x7fffffffLL) return set_error(FEDAGG_EINVAL, "fedagg_median: N too large");
-  if (K == P * R)
-    hipLaunchKernelGGL((median_lanes_kernel<P, R, true, E, BS>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, N,
-                       out);
-  else
-    hipLaunchKernelGGL((median_lanes_kernel<P, R, false, E, BS>), dim3(unsigned(grid)), dim3(BS), 0, st, src, K, N,
-                       out);
-  return check_launch("fedagg_median");
+  return launch_lanes("fedagg_median", median_lanes_kernel<P, R, true, E, BS>,
+                      median_lanes_kernel<P, R, false, E, BS>, K == P * R, P, BS, st, src, K, N, out);
 }
 
 // 16-bit rows with more than 128 clients, two columns per register: the lane
@@ -611,7 +599,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void me
   static_assert((PLANES && P == 1) || P == 2 || P == 4 || P == 8 || P == 16 || P == 32,
                 "2 to 32 lanes per column pair (1 for the bit-plane select)");
   static_assert(R == 32 || R == 64 || R == 128, "32, 64 or 128 values per lane");
-  constexpr int KMAX = P * R, PAD = 2;
+  constexpr int KMAX = P * R, PAD = kLanesSkew;
   __shared__ const uint16_t* rows[KMAX + PAD * P];
   __shared__ uint64_t offmask[FULL ? 1 : KMAX + PAD * P];
   const int t = threadIdx.x, sub = t & (P - 1);
@@ -634,13 +622,10 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void me
   const int64_t e = TAIL ? pairs : pair0 + (int64_t(blockIdx.x) * BS + t) / P;
   const uint64_t boff = uint64_t(TAIL || e < pairs ? e : pairs - 1) * 4u;
   auto word = [&](int j) -> uint32_t {
-    const int q = sub * (R + PAD) + j;
-    const uint64_t off = FULL ? boff : (boff & offmask[q]);
-    const auto row = reinterpret_cast<const char*>(rows[q]);
     if constexpr (TAIL)
-      return uint32_t(*as_global(reinterpret_cast<const uint16_t*>(row + off))) * 0x10001u;
+      return uint32_t(*lanes_slot_ptr<R, FULL, uint16_t>(rows, offmask, sub, j, boff)) * 0x10001u;
     else
-      return lanes_load(as_global(reinterpret_cast<const uint32_t*>(row + off)));
+      return lanes_load(lanes_slot_ptr<R, FULL, uint32_t>(rows, offmask, sub, j, boff));
   };
   uint32_t raw[R];
 #pragma unroll
@@ -1131,9 +1116,11 @@ int median_dispatch(const typename E::S* const* d_src, int32_t K, int64_t N, typ
         return launch_median_pk16_lanes<32, 128, E>(d_src, K, N, d_out, st);
       }
     }
-    if (K <= 256) return launch_median_lanes<4, 64, E>(d_src, K, N, d_out, st);  // 1.1 ms vs 1.4 for <2, 128> (4M cols)
-    if (K <= 512) return launch_median_lanes<4, 128, E>(d_src, K, N, d_out, st);
-    if (K <= 1024) return launch_median_lanes<8, 128, E>(d_src, K, N, d_out, st);
+    // up to 256 clients 4 x 64: 1.1 ms vs 1.4 for <2, 128> (4M cols)
+    if (K <= 1024)
+      return with_lane_tier(K, [&](auto p, auto r) {
+        return launch_median_lanes<decltype(p)::value, decltype(r)::value, E>(d_src, K, N, d_out, st);
+      });
     if (K <= 2048) return launch_median_lanes<16, 128, E>(d_src, K, N, d_out, st);
     // 32 lanes per column pay off against the radix select only well inside
     // their range (1M columns: 18.9 vs 18.7 ms at K = 2,049, 22.9 vs 35.4 ms

@@ -23,8 +23,8 @@ __device__ float g_nearmedian_wide_pad = __builtin_huge_valf();
 // trimmed_mean_lanes_kernel's form for fp32 rows (trimmed_wide.hip: P adjacent
 // lanes share a column, lane `sub` holding slots sub·R + j in registers, the
 // slot pointers staged in LDS with a skew, a padded slot reading +inf, every
-// NaN counted and replaced by +inf on arrival, the in-lane pairwise sort and
-// then every merge level, so that slot sub·R + j holds rank sub·R + j), then
+// NaN counted and replaced by +inf on arrival, then the whole sort
+// (lanes_sort_all), so that slot sub·R + j holds rank sub·R + j), then
 // nearmedian_mean_kernel's window (nearmedian.hip) instead of the centred
 // ranks.  With s[] the sorted slots, r = (K - 1) / 2, m = s[r], d = near_dist:
 //     lo_min = max(0, r - keep + 1),  lo_max = min(r, K - keep),
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void ne
   static_assert(P == 4 || P == 8, "4 or 8 lanes per column");
   static_assert(R == 64 || R == 128, "64 or 128 values per lane");
   static_assert(BS % 64 == 0 && 64 % P == 0, "whole waves of whole lane groups");
-  constexpr int KMAX = P * R, PAD = 2, NSLOT = KMAX + PAD * P;
+  constexpr int KMAX = P * R, PAD = kLanesSkew, NSLOT = KMAX + PAD * P;
   // the ring of partner positions: H chunks of R (+ 8) words per column
   constexpr int H = P / 2, W = H * R, CHUNK = R + 8;
   constexpr int COLW = H * CHUNK + (33 - (H * CHUNK) % 32) % 32;  // 1 mod 32 words per column
@@ -118,10 +118,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void ne
 #pragma unroll
   for (int j = 0; j < R; ++j) {
     if (j % 16 == 0 && j) __builtin_amdgcn_sched_barrier(0);
-    const int q = sub * (R + PAD) + j;
-    const uint64_t off = FULL ? boff : (boff & offmask[q]);
-    const auto row = reinterpret_cast<const char*>(rows[q]);
-    v[j] = lanes_load(as_global(reinterpret_cast<const float*>(row + off)));
+    v[j] = lanes_load(lanes_slot_ptr<R, FULL, float>(rows, offmask, sub, j, boff));
   }
   // after every load is in flight
   __builtin_amdgcn_sched_barrier(0);
@@ -133,8 +130,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void ne
     v[j] = n ? __builtin_huge_valf() : v[j];
   }
   nans = lanes_count_sum<P>(nans);
-  pairwise_sort<R>(v);
-  lanes_merge_levels<2, 2 * P, R>(v, sub);  // every level, G = P included
+  lanes_sort_all<P>(v, sub);
   __syncthreads();  // the pointer table is dead in every wave: its LDS becomes the ring
 
   // m = s[r]
@@ -224,18 +220,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void ne
 
 template <int P, int R, int BS = 256>
 int launch_nearmedian_lanes(const float* const* src, int K, int64_t N, int keep, float* out, hipStream_t st) {
-  const unsigned grid = unsigned((N * P + BS - 1) / BS);  // the caller bounded it
-  if (K == P * R)
-    hipLaunchKernelGGL((nearmedian_mean_lanes_kernel<P, R, true, BS>), dim3(grid), dim3(BS), 0, st, src, K, N, keep,
-                       out);
-  else
-    hipLaunchKernelGGL((nearmedian_mean_lanes_kernel<P, R, false, BS>), dim3(grid), dim3(BS), 0, st, src, K, N, keep,
-                       out);
-  return check_launch("fedagg_nearmedian_mean_wide_f32");
+  return launch_lanes("fedagg_nearmedian_mean_wide_f32", nearmedian_mean_lanes_kernel<P, R, true, BS>,
+                      nearmedian_mean_lanes_kernel<P, R, false, BS>, K == P * R, P, BS, st, src, K, N, out, keep);
 }
-
-// lanes per column of the tier holding K rows (trimmed_wide.hip's tiers)
-constexpr int wide_lanes(int K) { return K <= 512 ? 4 : 8; }
 
 }  // namespace
 
@@ -253,14 +240,11 @@ int fedagg_nearmedian_mean_wide_f32(const float* const* d_src, int32_t K, int64_
     return set_error(FEDAGG_ENOKERNEL, "fedagg_nearmedian_mean_wide_f32: the kernel holds at most " +
                                            std::to_string(FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS) + " rows (K = " +
                                            std::to_string(K) + ")");
-  // 256 lanes per block, wide_lanes(K) of them per column
-  if (N > (int64_t(0x7fffffff) * 256) / wide_lanes(K))
-    return set_error(FEDAGG_EINVAL, "fedagg_nearmedian_mean_wide_f32: N too large");
-  if (N == 0) return FEDAGG_OK;
+  if (N == 0) return FEDAGG_OK;  // launch_lanes bounds the grid ("N too large")
   auto st = reinterpret_cast<hipStream_t>(stream);
-  if (K <= 256) return launch_nearmedian_lanes<4, 64>(d_src, K, N, keep, d_out, st);
-  if (K <= 512) return launch_nearmedian_lanes<4, 128>(d_src, K, N, keep, d_out, st);
-  return launch_nearmedian_lanes<8, 128>(d_src, K, N, keep, d_out, st);
+  return with_lane_tier(K, [&](auto p, auto r) {
+    return launch_nearmedian_lanes<decltype(p)::value, decltype(r)::value>(d_src, K, N, keep, d_out, st);
+  });
 }
 
 }  // extern "C"

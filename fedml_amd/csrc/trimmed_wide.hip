@@ -23,9 +23,8 @@ namespace {
 // its KMAX = P·R in registers, the slot pointers staged in LDS with a skew
 // per lane group, a padded slot pointing at a constant with its column offset
 // masked to 0.  The differences are trimmed_mean_kernel's (trimmed.hip):
-//   - every rank is needed, so after the in-lane pairwise sort EVERY merge
-//     level runs, the last one (G = P) in full; afterwards slot sub·R + j
-//     holds rank sub·R + j;
+//   - every rank is needed, so the whole sort runs (lanes_sort_all, lanesort.h):
+//     afterwards slot sub·R + j holds rank sub·R + j;
 //   - padding is +inf only, all of it above rank K - 1;
 //   - no NaN enters the networks: each is counted and replaced by +inf as it
 //     arrives, the counts added over the P lanes of the column.
@@ -41,8 +40,6 @@ namespace {
 template <class E>
 __device__ typename E::S g_trimmed_wide_pad = trim_pos_inf<E>();
 
-// lanes_count_sum: lanesort.h (shared with nearmedian_wide.hip)
-
 template <int P, int R, bool FULL, class E, int BS = 256>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void trimmed_mean_lanes_kernel(
     const typename E::S* const* __restrict__ src, int K, int64_t N, int trim, typename E::S* __restrict__ out) {
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void tr
   static_assert(P == 2 || P == 4 || P == 8 || P == 16, "2 to 16 lanes per column");
   static_assert(R == 64 || R == 128, "64 or 128 values per lane");
   static_assert(BS % 64 == 0 && 64 % P == 0, "whole waves of whole lane groups");
-  constexpr int KMAX = P * R, PAD = 2;
+  constexpr int KMAX = P * R, PAD = kLanesSkew;
   // row pointer of every slot, skewed by PAD entries per lane group
   // (median_lanes_kernel); a padded slot reads the +inf constant at offset 0
   __shared__ const S* rows[KMAX + PAD * P];
@@ -77,10 +74,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void tr
 #pragma unroll
   for (int j = 0; j < R; ++j) {
     if (j % 16 == 0 && j) __builtin_amdgcn_sched_barrier(0);
-    const int q = sub * (R + PAD) + j;
-    const uint64_t off = FULL ? boff : (boff & offmask[q]);
-    const auto row = reinterpret_cast<const char*>(rows[q]);
-    S x = lanes_load(as_global(reinterpret_cast<const S*>(row + off)));
+    S x = lanes_load(lanes_slot_ptr<R, FULL, S>(rows, offmask, sub, j, boff));
     if constexpr (sizeof(S) == 2) {
       // 16-bit rows test the raw value as it widens (trimmed_mean_kernel)
       const bool n = E::raw_nan(x);
@@ -100,8 +94,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void tr
     }
   }
   nans = lanes_count_sum<P>(nans);
-  pairwise_sort<R>(v);
-  lanes_merge_levels<2, 2 * P, R>(v, sub);  // every level, G = P included
+  lanes_sort_all<P>(v, sub);
   // the kept ranks as what the chain adds, everything else as -0.f
   const uint32_t kept = uint32_t(K - 2 * trim);
   const int first = sub * R - trim;
@@ -132,26 +125,16 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void tr
 template <int P, int R, class E, int BS = 256>
 int launch_trimmed_lanes(const typename E::S* const* src, int K, int64_t N, int trim, typename E::S* out,
                          hipStream_t st) {
-  const unsigned grid = unsigned((N * P + BS - 1) / BS);  // the caller bounded it
-  if (K == P * R)
-    hipLaunchKernelGGL((trimmed_mean_lanes_kernel<P, R, true, E, BS>), dim3(grid), dim3(BS), 0, st, src, K, N, trim,
-                       out);
-  else
-    hipLaunchKernelGGL((trimmed_mean_lanes_kernel<P, R, false, E, BS>), dim3(grid), dim3(BS), 0, st, src, K, N, trim,
-                       out);
-  return check_launch("fedagg_trimmed_mean_wide");
+  return launch_lanes("fedagg_trimmed_mean_wide", trimmed_mean_lanes_kernel<P, R, true, E, BS>,
+                      trimmed_mean_lanes_kernel<P, R, false, E, BS>, K == P * R, P, BS, st, src, K, N, out, trim);
 }
-
-// lanes per column of the tier holding K clients: 4 x 64 up to 256, 4 x 128 up
-// to 512, 8 x 128 up to 1024 (the fp32 median's tiers)
-constexpr int wide_lanes(int K) { return K <= 512 ? 4 : 8; }
 
 template <class E>
 int trimmed_wide_dispatch(const typename E::S* const* d_src, int32_t K, int64_t N, int32_t trim,
                           typename E::S* d_out, hipStream_t st) {
-  if (K <= 256) return launch_trimmed_lanes<4, 64, E>(d_src, K, N, trim, d_out, st);
-  if (K <= 512) return launch_trimmed_lanes<4, 128, E>(d_src, K, N, trim, d_out, st);
-  return launch_trimmed_lanes<8, 128, E>(d_src, K, N, trim, d_out, st);
+  return with_lane_tier(K, [&](auto p, auto r) {
+    return launch_trimmed_lanes<decltype(p)::value, decltype(r)::value, E>(d_src, K, N, trim, d_out, st);
+  });
 }
 
 }  // namespace
@@ -172,10 +155,7 @@ int fedagg_trimmed_mean_wide(int32_t dtype, const void* const* d_src, int32_t K,
     return set_error(FEDAGG_ENOKERNEL, "fedagg_trimmed_mean_wide: the kernel holds at most " +
                                            std::to_string(FEDAGG_TRIMMED_WIDE_MAX_CLIENTS) + " clients (K = " +
                                            std::to_string(K) + ")");
-  // 256 lanes per block, wide_lanes(K) of them per column
-  if (N > (int64_t(0x7fffffff) * 256) / wide_lanes(K))
-    return set_error(FEDAGG_EINVAL, "fedagg_trimmed_mean_wide: N too large");
-  if (N == 0) return FEDAGG_OK;
+  if (N == 0) return FEDAGG_OK;  // launch_lanes bounds the grid ("N too large")
   auto st = reinterpret_cast<hipStream_t>(stream);
   switch (dtype) {
     case FEDAGG_DT_F32:

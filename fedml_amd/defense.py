@@ -319,12 +319,15 @@ TRIMMED_WIDE_MAX_CLIENTS = nat.TRIMMED_WIDE_MAX_CLIENTS
 TRIMMED_WIDE_AUTO = {256: True, 512: True, 1024: True}
 
 
+def _tier_auto(table: dict, max_clients: int, K: int) -> bool:
+    """A *_WIDE_AUTO table's entry for K clients; False above max_clients."""
+    return K <= max_clients and table[min(t for t in table if K <= t)]
+
+
 def trimmed_wide_auto(K: int) -> bool:
     """Whether coordinate_wise_trimmed_mean runs the wide kernel for K clients
     above TRIMMED_MAX_CLIENTS (TRIMMED_WIDE_AUTO)."""
-    if K > TRIMMED_WIDE_MAX_CLIENTS:
-        return False
-    return TRIMMED_WIDE_AUTO[min(t for t in TRIMMED_WIDE_AUTO if K <= t)]
+    return _tier_auto(TRIMMED_WIDE_AUTO, TRIMMED_WIDE_MAX_CLIENTS, K)
 
 
 def trimmed_mean_rows_wide(d_ptrs: torch.Tensor, K: int, N: int, trim: int, out: torch.Tensor) -> None:
@@ -1198,9 +1201,7 @@ NEARMEDIAN_WIDE_AUTO = {256: True, 512: True, 1024: True}
 def nearmedian_wide_auto(theta: int) -> bool:
     """Whether bulyan runs the wide kernel for theta selected clients above
     NEARMEDIAN_MAX_CLIENTS (NEARMEDIAN_WIDE_AUTO)."""
-    if theta > NEARMEDIAN_WIDE_MAX_CLIENTS:
-        return False
-    return NEARMEDIAN_WIDE_AUTO[min(t for t in NEARMEDIAN_WIDE_AUTO if theta <= t)]
+    return _tier_auto(NEARMEDIAN_WIDE_AUTO, NEARMEDIAN_WIDE_MAX_CLIENTS, theta)
 
 
 def nearmedian_mean_rows_wide(d_ptrs: torch.Tensor, K: int, N: int, keep: int, out: torch.Tensor) -> None:

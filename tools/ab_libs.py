@@ -4,11 +4,22 @@ FedAvg, each build's launch timed back to back (`--launches` per sample),
 the builds interleaved round by round, medians reported.
 
     python tools/ab_libs.py fedml_amd/lib/ab/libfedagg_r05start.so fedml_amd/lib/libfedagg.so
+
+`--cases lanes` times the lane-group kernels above 128 clients instead (the
+median, the wide trimmed mean and the wide nearest-to-median mean, each tier
+at its full K and at one padded K): any number of builds, all of them writing
+the SAME output buffer (NOTES.md: a buffer of its own per build read 2.5 %
+apart), the order of the builds reversed every other round, outputs compared
+bit for bit with the first build's, median and min-max per build.  A second
+copy of the first build's file is the control:
+
+    python tools/ab_libs.py --cases lanes lib/ab/parent.so lib/ab/parent_copy.so lib/libfedagg.so
 """
 from __future__ import annotations
 
 import argparse
 import ctypes
+import json
 import os
 import statistics
 import sys
@@ -30,12 +41,97 @@ def load(path):
     return lib
 
 
+# tier (the full K), a padded K of it, columns; the last two are the median's alone
+LANE_TIERS = [(256, 200, 4_194_304), (512, 384, 4_194_304), (1024, 700, 4_194_304),
+              (2048, 1500, 1_048_576), (4096, 3000, 1_048_576)]
+LANE_DT = {"f32": (nat.DT_F32, torch.float32), "bf16": (nat.DT_BF16, torch.bfloat16),
+           "f16": (nat.DT_F16, torch.float16)}
+
+
+def lanes(a):
+    dev = torch.device("cuda:0")
+    libs = [ctypes.CDLL(os.path.abspath(p), mode=ctypes.RTLD_LOCAL) for p in a.libs]
+    for lib in libs:
+        lib.fedagg_median.argtypes = [I32, P, I32, I64, P, U32, P]
+        lib.fedagg_trimmed_mean_wide.argtypes = [I32, P, I32, I64, I32, P, U32, P]
+        lib.fedagg_nearmedian_mean_wide_f32.argtypes = [P, I32, I64, I32, P, U32, P]
+    st = nat.stream_handle()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    names = [os.path.basename(p) for p in a.libs]
+    results = []
+
+    def wanted(name):
+        return not a.only or any(w in name for w in a.only.split(","))
+
+    for tier, padded, N in LANE_TIERS:
+        for dname, (code, dt) in LANE_DT.items():
+            if not any(wanted(f"{op}-K{k}-{dname}") for op in ("median", "median16", "trimmed", "nearmedian")
+                       for k in (tier, padded)):
+                continue  # no rows for a tier that --only leaves out
+            rows = torch.empty((tier, N), device=dev, dtype=dt).normal_(0.0, 0.05)
+            ptrs = torch.tensor([rows[i].data_ptr() for i in range(tier)], dtype=torch.int64, device=dev)
+            out = torch.empty(N, device=dev, dtype=dt)
+            o, s = out.data_ptr(), ptrs.data_ptr()
+            for K in (tier, padded):
+                # flags 0: the widening kernels for 16-bit rows too; median16: the packed ones
+                cases = [("median", lambda lib: lib.fedagg_median(code, s, K, N, o, 0, st))]
+                if dt != torch.float32 and tier > 1024:
+                    cases.append(("median16", lambda lib: lib.fedagg_median(code, s, K, N, o, nat.FEDAGG_ALIGNED16, st)))
+                if tier <= 1024:
+                    cases.append(("trimmed", lambda lib: lib.fedagg_trimmed_mean_wide(code, s, K, N, K // 10, o, 0, st)))
+                    if dt == torch.float32:
+                        cases.append(("nearmedian", lambda lib: lib.fedagg_nearmedian_mean_wide_f32(
+                            s, K, N, K - 2 * (K // 8), o, 0, st)))
+                for op, fn in cases:
+                    name = f"{op}-K{K}-{dname}"
+                    if not wanted(name):
+                        continue
+                    ref = None
+                    for lib, n in zip(libs, names):
+                        out.zero_()
+                        nat.check(fn(lib), name)
+                        torch.cuda.synchronize()
+                        bits = out.view(torch.int16 if out.element_size() == 2 else torch.int32).clone()
+                        ref = bits if ref is None else ref
+                        assert torch.equal(bits, ref), f"{name}: {n} differs from {names[0]}"
+                    times = [[] for _ in libs]
+                    for r in range(a.rounds):
+                        for i in (range(len(libs)) if r % 2 == 0 else reversed(range(len(libs)))):
+                            fn(libs[i])
+                            ev0.record()
+                            for _ in range(a.launches):
+                                fn(libs[i])
+                            ev1.record()
+                            ev1.synchronize()
+                            times[i].append(ev0.elapsed_time(ev1) / a.launches)
+                    res = {"case": name, "N": N, "launches": a.launches, "rounds": a.rounds, "bit_identical": True,
+                           "builds": {n: {"median_ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t)}
+                                      for n, t in zip(names, times)}}
+                    results.append(res)
+                    print(f"{name:22s} " + "   ".join(f"{n}: {statistics.median(t):.4f} ({min(t):.4f}-{max(t):.4f})"
+                                                      for n, t in zip(names, times)), flush=True)
+                    if a.out:
+                        with open(a.out, "w") as f:
+                            json.dump(results, f, indent=1)
+            del rows, ptrs, out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("libs", nargs=2)
-    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("libs", nargs="+")
+    ap.add_argument("--cases", default="fedavg", choices=["fedavg", "lanes"])
+    ap.add_argument("--only", default="", help="lanes: the cases whose name (op-K<K>-<dtype>) contains one of "
+                                               "these, comma-separated (--only=-f32,trimmed-)")
+    ap.add_argument("--out", default=None, help="lanes: the results as JSON")
+    ap.add_argument("--rounds", type=int, default=None, help="samples per build (default 7; lanes: 10)")
     ap.add_argument("--launches", type=int, default=20)
     a = ap.parse_args()
+    if a.rounds is None:
+        a.rounds = 10 if a.cases == "lanes" else 7
+    if a.cases == "lanes":
+        return lanes(a)
+    if len(a.libs) != 2:
+        ap.error("--cases fedavg takes two libraries")
     dev = torch.device("cuda:0")
     libs = [load(p) for p in a.libs]
     st = nat.stream_handle()
