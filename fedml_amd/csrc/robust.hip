@@ -618,6 +618,7 @@ __global__ __launch_bounds__(256) void tri_finish_kernel(const double* __restric
 // the Krum selections and D against the exact-difference kernel).
 constexpr int kGramMax = 128;          // clients the Gram kernel holds (8 groups of 16)
 constexpr int kGramBlocksPerCU = 2;    // 2 x (2 stage buffers of 128 rows) = 143 KB of LDS per CU
+constexpr int kGramMaxGroups = 256;    // pairgram_split8_kernel: one block per CU, so at most 256 chunk groups
 
 __host__ __device__ inline int gram_groups(int K) { return (K + 15) / 16; }
 __host__ __device__ inline int gram_tiles(int K) {
@@ -1150,7 +1151,9 @@ int64_t fedagg_robust_work_len(int32_t kind, int32_t K, int64_t n_chunks) {
   if (kind == FEDAGG_WORK_DIST2) return int64_t(K) * grid_groups(4, n_chunks, 0, 0);
   if (kind == FEDAGG_WORK_PAIRGRAM) {
     if (K > kGramMax) return -1;
-    const int G = grid_groups(4096 / (256 * kGramBlocksPerCU), n_chunks, 0, 0);
+    // the groups the split kernel runs, not the 512 a two-blocks-per-CU grid would
+    int G = grid_groups(4096 / (256 * kGramBlocksPerCU), n_chunks, 0, 0);
+    if (G > kGramMaxGroups) G = kGramMaxGroups;
     return int64_t(G) * gram_tiles(K) * 256 + int64_t(K) * K;
   }
   if (kind == FEDAGG_WORK_PAIRDIST2) {
@@ -1230,6 +1233,7 @@ int fedagg_pairgram2_f32(const float* const* d_src, int32_t K, const int64_t* d_
   if (work_len < per + mat)
     return set_error(FEDAGG_EINVAL, "fedagg_pairgram2_f32: workspace too small (fedagg_robust_work_len)");
   int G = grid_groups(4096 / (256 * kGramBlocksPerCU), n_chunks, work_len - mat, per);
+  if (G > kGramMaxGroups) G = kGramMaxGroups;  // one block per CU
   double* M = d_work + int64_t(G) * per;
   {
     auto kern = pairgram_split8_kernel<8>;
@@ -1243,9 +1247,7 @@ int fedagg_pairgram2_f32(const float* const* d_src, int32_t K, const int64_t* d_
       case 7: kern = pairgram_split8_kernel<7>; break;
       default: break;
     }
-    const int G1 = G < 256 ? G : 256;  // one block per CU
-    hipLaunchKernelGGL(kern, dim3(unsigned(G1)), dim3(kSplit8BS), 0, st, d_src, K, d_chunks, n_chunks, G1, d_work);
-    G = G1;
+    hipLaunchKernelGGL(kern, dim3(unsigned(G)), dim3(kSplit8BS), 0, st, d_src, K, d_chunks, n_chunks, G, d_work);
   }
   hipLaunchKernelGGL(gram_sum_kernel, dim3(unsigned((per + 63) / 64)), dim3(256), 0, st, d_work, G, K, M);
   hipLaunchKernelGGL(gram_dist_kernel, dim3(unsigned((mat + 255) / 256)), dim3(256), 0, st, M, K, d_out);

@@ -480,6 +480,18 @@ int fedagg_nearmedian_mean_wide_f32(const float* const* d_src, int32_t K,
  * results are deterministic.  d_work holds at least
  * fedagg_robust_work_len(kind, K, n_chunks) doubles.
  *
+ * A smaller workspace is accepted as long as it holds one chunk group's
+ * partials (K doubles for dist2 and wsum_dist2; 16 doubles per 4 x 4 client
+ * block of the pair triangle up to 128 clients and 4,096 per 64 x 64 client
+ * tile above; 256 per 16 x 16 client tile of the Gram, plus its K x K matrix
+ * once); below that the call is FEDAGG_EINVAL.  The entry point then runs
+ * floor(work_len / doubles per group) chunk groups instead of the default
+ * count (for the Gram after setting the K x K doubles aside): fewer blocks, a
+ * different but still fixed fp64 summation order, results within the same
+ * bounds.  work_len is the number of doubles the call may write: nothing at
+ * or past d_work + work_len is touched.  (tests/test_gpu_chunk_groups.py
+ * chooses the group count this way.)
+ *
  * fedagg_dist2_f32 replaces the per-client torch.norm(vec_local - vec_global)
  * of NormDiffClippingDefense._get_clipped_norm_diff
  * (defense/norm_diff_clipping_defense.py:38-42) and CClip's
