@@ -1000,6 +1000,26 @@ __global__ __launch_bounds__(kSplit8BS, 1) void pairgram_split8_kernel(const flo
 }
 
 
+// sum over g < G of p[g * stride] for the 256 threads of a finish block
+// (lane = element, wave qq = quarter): wave qq adds the groups qq, qq + 4, ...
+// eight loads in flight, and the four quarter sums are added in a fixed
+// order.  Every thread returns its lane's total.
+__device__ __forceinline__ double quartered_sum(const double* __restrict__ p, int64_t stride, int G,
+                                                double (&quarter)[4][64], int lane, int qq) {
+  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int gg = qq;
+  for (; gg + 28 < G; gg += 32) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s[u] += p[int64_t(gg + 4 * u) * stride];
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+    if (gg + 4 * u < G) s[u] += p[int64_t(gg + 4 * u) * stride];
+  quarter[qq][lane] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+  __syncthreads();
+  return (quarter[0][lane] + quarter[1][lane]) + (quarter[2][lane] + quarter[3][lane]);
+}
+
 // M (K x K, fp64, both triangles) = the tiles' partials summed over the chunk
 // groups in four fixed-order quarters (as tri_finish_kernel)
 __global__ __launch_bounds__(256) void gram_sum_kernel(const double* __restrict__ partial, int G, int K,
@@ -1009,20 +1029,8 @@ __global__ __launch_bounds__(256) void gram_sum_kernel(const double* __restrict_
   const int lane = threadIdx.x & 63, qq = threadIdx.x >> 6;
   const int e = blockIdx.x * 64 + lane;
   const int ec = e < E ? e : E - 1;
-  const double* p = partial + ec;
-  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  int gg = qq;
-  for (; gg + 28 < G; gg += 32) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s[u] += p[int64_t(gg + 4 * u) * E];
-  }
-#pragma unroll
-  for (int u = 0; u < 8; ++u)
-    if (gg + 4 * u < G) s[u] += p[int64_t(gg + 4 * u) * E];
-  quarter[qq][lane] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-  __syncthreads();
+  const double v = quartered_sum(partial + ec, E, G, quarter, lane, qq);
   if (qq != 0 || e >= E) return;
-  const double v = (quarter[0][lane] + quarter[1][lane]) + (quarter[2][lane] + quarter[3][lane]);
   const int2 ab = gram_tile(e >> 8, nb);
   const int row = 16 * ab.x + ((e >> 4) & 15), col = 16 * ab.y + (e & 15);
   if (row >= K || col >= K) return;
@@ -1043,6 +1051,228 @@ __global__ __launch_bounds__(256) void gram_dist_kernel(const double* __restrict
   // non-finite client (inf elements, or squares beyond fp32) reaches
   // gram_condition and sends "auto" to the exact kernel
   D[e] = i == j ? 0.0 : (d < 0.0 ? 0.0 : d);
+}
+
+// ---------------------------------------------------------------------------
+// The split Gram for up to 1024 clients (fedagg_pairgram2_wide_f32):
+// pairdist_kernel's decomposition with pairgram_split8_kernel's inner loop.
+// The K x K pair matrix is cut into 64-client tiles (I <= J); a block owns one
+// tile pair over the chunk groups g, g + G, ...  No block sees all K rows, so
+// the centre r of c = fl(x - r) is an argument: one fp32 row indexed like the
+// client rows (the caller passes the client mean; D is translation invariant,
+// r only decides conditioning).
+//
+// Per 64-column stage the 8 waves stage I's 64 rows and J's 64 rows (16 rows
+// a wave, four 16-byte loads per lane), subtract the centre and split once per
+// element into the three bf16 planes: 128 plane rows of kSplitRB bytes, the
+// NB = 8 budget of pairgram_split8_kernel, double-buffered, one barrier per
+// stage, raw rows prefetched two stages ahead.  An off-diagonal pair has the
+// 4 x 4 = 16 cross group-tiles: wave w takes A group w / 2 against the two B
+// groups 2 (w % 2), + 1, so its A fragments are read once for two tiles.  A
+// diagonal pair stages 64 rows (waves 0 - 3) and has the 10 tiles of the group
+// triangle (kWideDiag: 3, 3, 2, 2 per SIMD).  Rows are read with plain loads,
+// not non-temporal ones: each 64-row panel is read by every block whose pair
+// holds its tile, and the grid runs tile pairs fastest, chunk groups slowest,
+// so blocks resident together read the same columns.  At K = 1024 the L2
+// absorbs about a third of the 17-fold re-read (FETCH_SIZE 11.8x the rows);
+// an XCD-grouped block order did not change the time (NOTES.md 5c).
+// Partials: [g][tile pair][16 group-tiles a * 4 + b][16 x 16]; a diagonal pair
+// writes the slots a <= b only and gram_wide_sum_kernel reads no other.
+constexpr int kWideMax = FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS;
+constexpr int kWideBS = 512;
+constexpr int kWidePlane = 2 * kPT * kSplitRB;  // a plane: tile I's 64 rows, then tile J's
+constexpr int kWideBlocks = 2048;               // blocks the grid aims for (one per CU resident)
+// a diagonal pair's tiles per wave: {A group, first B group, tiles}; waves w
+// and w + 4 sit on one SIMD
+__constant__ constexpr int kWideDiag[8][3] = {{0, 0, 2}, {1, 1, 2}, {2, 2, 2}, {1, 3, 1},
+                                              {0, 2, 1}, {0, 3, 1}, {0, 0, 0}, {3, 3, 1}};
+
+// c = h + m + l, four columns of one row, into the three planes at d
+__device__ __forceinline__ void split3_store(f32x4 cc, unsigned char* d, int plane) {
+  const uint32_t h01 = pk_bf16(cc.x, cc.y), h23 = pk_bf16(cc.z, cc.w);
+  const float e0 = cc.x - bf16_lo(h01), e1 = cc.y - bf16_hi(h01);
+  const float e2 = cc.z - bf16_lo(h23), e3 = cc.w - bf16_hi(h23);
+  const uint32_t m01 = pk_bf16(e0, e1), m23 = pk_bf16(e2, e3);
+  const uint32_t l01 = pk_bf16(e0 - bf16_lo(m01), e1 - bf16_hi(m01));
+  const uint32_t l23 = pk_bf16(e2 - bf16_lo(m23), e3 - bf16_hi(m23));
+  *reinterpret_cast<u32x2v*>(d) = u32x2v{h01, h23};
+  *reinterpret_cast<u32x2v*>(d + plane) = u32x2v{m01, m23};
+  *reinterpret_cast<u32x2v*>(d + 2 * plane) = u32x2v{l01, l23};
+}
+
+__global__ __launch_bounds__(kWideBS, 1) void pairgram_wide_kernel(const float* const* __restrict__ src, int K,
+                                                                   const float* __restrict__ center,
+                                                                   const int64_t* __restrict__ chunks,
+                                                                   int64_t n_chunks, int G,
+                                                                   double* __restrict__ partial) {
+  constexpr int LPW = 4;  // 16-byte loads per lane and stage: 16 rows a wave, 4 rows per wave-load
+  __shared__ __attribute__((aligned(16))) unsigned char sP[2][3 * kWidePlane];
+  const int tp = blockIdx.x, g = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int i16 = lane & 15, q = lane >> 4;
+  const int2 tile = tile_of(tp, (K + kPT - 1) / kPT);
+  const bool diag = tile.x == tile.y;
+  const bool stager = !diag || wave < 4;  // a diagonal pair has 64 rows to stage
+  const float* rowp[LPW];
+  bool rlive[LPW];
+#pragma unroll
+  for (int u = 0; u < LPW; ++u) {
+    const int lr = wave * 16 + 4 * u + q;  // plane row
+    const int cl = lr < kPT ? tile.x * kPT + lr : tile.y * kPT + (lr - kPT);
+    rlive[u] = stager && cl < K;
+    rowp[u] = src[rlive[u] ? cl : 0];  // a row past K reads row 0: its Gram entries are never summed
+  }
+  // this wave's tiles: A group ga against B groups gb, gb + 1 (nt of them)
+  const int ga = diag ? kWideDiag[wave][0] : wave >> 1;
+  const int gb = diag ? kWideDiag[wave][1] : 4 + 2 * (wave & 1);
+  const int nt = diag ? kWideDiag[wave][2] : 2;
+  double acc64[2][4];
+  f32x4v acc[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    acc[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc64[j][r] = 0.0;
+  }
+  int64_t c = g;
+  int s0 = 0;
+  f32x4 v[2][LPW], cen[2];
+  auto fetch = [&](f32x4 (&vv)[LPW], f32x4& rr) __attribute__((always_inline)) {
+    if (c >= n_chunks) return false;
+    const int len = int(chunks[2 * c + 1]);
+    const int64_t col0 = chunks[2 * c] + s0;
+    const int w = len - s0 < kStage ? len - s0 : kStage;
+    const int c4 = 4 * i16;
+    if (stager) {
+      if (w == kStage) {
+#pragma unroll
+        for (int u = 0; u < LPW; ++u) vv[u] = ld4<false>(rowp[u] + col0 + c4);
+        rr = ld4<false>(center + col0 + c4);
+      } else {  // columns past w read 0 in the rows and in the centre: c = 0
+#pragma unroll
+        for (int u = 0; u < LPW; ++u) {
+          const float* pp = rowp[u] + col0;
+          const bool ok = rlive[u];
+          vv[u].x = ok && c4 < w ? gptr(pp)[c4] : 0.f;
+          vv[u].y = ok && c4 + 1 < w ? gptr(pp)[c4 + 1] : 0.f;
+          vv[u].z = ok && c4 + 2 < w ? gptr(pp)[c4 + 2] : 0.f;
+          vv[u].w = ok && c4 + 3 < w ? gptr(pp)[c4 + 3] : 0.f;
+        }
+        const float* pc = center + col0;
+        rr.x = c4 < w ? gptr(pc)[c4] : 0.f;
+        rr.y = c4 + 1 < w ? gptr(pc)[c4 + 1] : 0.f;
+        rr.z = c4 + 2 < w ? gptr(pc)[c4 + 2] : 0.f;
+        rr.w = c4 + 3 < w ? gptr(pc)[c4 + 3] : 0.f;
+      }
+    }
+    s0 += kStage;
+    if (s0 >= len) {
+      s0 = 0;
+      c += G;
+    }
+    return true;
+  };
+  auto stage_split = [&](const f32x4 (&vv)[LPW], const f32x4& rr, unsigned char* P) __attribute__((always_inline)) {
+    if (!stager) return;
+#pragma unroll
+    for (int u = 0; u < LPW; ++u)
+      split3_store(vv[u] - rr, P + (wave * 16 + 4 * u + q) * kSplitRB + 8 * i16, kWidePlane);
+  };
+  int unfolded = 0;
+  auto fold = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      // the 16 wait states between the MFMA chain and this VALU read, as in
+      // pairgram_split8_kernel (tools/mfma_hazards.py checks every build)
+      asm volatile("s_nop 15" : "+v"(acc[j]));
+      acc64[j][0] += double(acc[j].x);
+      acc64[j][1] += double(acc[j].y);
+      acc64[j][2] += double(acc[j].z);
+      acc64[j][3] += double(acc[j].w);
+      acc[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    }
+    unfolded = 0;
+  };
+  const int fo = i16 * kSplitRB + 16 * q;
+  auto compute = [&](const unsigned char* P) __attribute__((always_inline)) {
+    if (nt > 0) {
+      const unsigned char* fp = P + fo;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8v A[3], B[2][3];
+        split_frag<kWidePlane>(fp, ga, ks, A);
+        split_frag<kWidePlane>(fp, gb, ks, B[0]);
+        split_frag<kWidePlane>(fp, nt > 1 ? gb + 1 : gb, ks, B[1]);
+        acc[0] = split_mfma6(A, B[0], acc[0]);
+        if (nt > 1) acc[1] = split_mfma6(A, B[1], acc[1]);
+      }
+    }
+    if (++unfolded == kSplitFold) fold();
+  };
+  // prologue: stages 0 and 1 loaded, stage 0 split
+  bool h0 = fetch(v[0], cen[0]);
+  bool h1 = h0 && fetch(v[1], cen[1]);
+  if (h0) {
+    stage_split(v[0], cen[0], sP[0]);
+    bool h2 = h1 && fetch(v[0], cen[0]);  // stage 2
+    lds_barrier();
+    // iteration k (two at a time, so the register sets are static): split
+    // stage k + 1 into the free plane buffer, issue stage k + 3's loads into
+    // the freed registers, compute stage k, barrier
+    auto iter = [&](auto cur_tag, bool& hn, bool& hnn) __attribute__((always_inline)) {
+      constexpr int C = decltype(cur_tag)::value;  // k % 2
+      // hn: stage k + 1 exists (in v[C ^ 1]); hnn: stage k + 2 (in v[C])
+      bool hnnn = false;
+      if (hn) {
+        stage_split(v[C ^ 1], cen[C ^ 1], sP[C ^ 1]);
+        hnnn = hnn && fetch(v[C ^ 1], cen[C ^ 1]);  // stage k + 3
+      }
+      compute(sP[C]);
+      lds_barrier();
+      const bool more = hn;
+      hn = hnn;
+      hnn = hnnn;
+      return more;
+    };
+    bool hn = h1, hnn = h2;
+    while (true) {
+      if (!iter(std::integral_constant<int, 0>{}, hn, hnn)) break;
+      if (!iter(std::integral_constant<int, 1>{}, hn, hnn)) break;
+    }
+  }
+  if (unfolded) fold();
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (j < nt) {
+      const int slot = ga * 4 + (gb + j - (diag ? 0 : 4));
+      double* out = partial + ((int64_t(g) * gridDim.x + tp) * 16 + slot) * 256;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[(4 * q + r) * 16 + i16] = acc64[j][r];
+    }
+  }
+}
+
+// M (K x K, fp64, both triangles) = the tile pairs' partials summed over the
+// chunk groups (gram_sum_kernel's order).  A block owns 64 entries of one
+// 16 x 16 group-tile; a diagonal pair's tiles a > b do not exist and come from
+// their mirrors.
+__global__ __launch_bounds__(256) void gram_wide_sum_kernel(const double* __restrict__ partial, int G, int K,
+                                                            double* __restrict__ M) {
+  __shared__ double quarter[4][64];
+  const int T = (K + kPT - 1) / kPT;
+  const int64_t E = int64_t(T * (T + 1) / 2) * (kPT * kPT);
+  const int lane = threadIdx.x & 63, qq = threadIdx.x >> 6;
+  const int e = blockIdx.x * 64 + lane;
+  const int2 tile = tile_of(e >> 12, T);
+  const int a = (e >> 10) & 3, b = (e >> 8) & 3;
+  const bool dg = tile.x == tile.y;
+  if (dg && a > b) return;  // block-uniform
+  const double v = quartered_sum(partial + e, E, G, quarter, lane, qq);
+  if (qq != 0) return;
+  const int row = tile.x * kPT + 16 * a + ((e >> 4) & 15), col = tile.y * kPT + 16 * b + (e & 15);
+  if (row >= K || col >= K) return;
+  M[int64_t(row) * K + col] = v;  // a diagonal group-tile writes both orders itself
+  if (!(dg && a == b)) M[int64_t(col) * K + row] = v;
 }
 
 // ---------------------------------------------------------------------------
@@ -1125,6 +1355,9 @@ int grid_groups(int per_group_blocks, int64_t n_chunks, int64_t work_len, int64_
 }
 
 int pair_tiles(int K) { const int T = (K + kPT - 1) / kPT; return T * (T + 1) / 2; }
+// grid_groups' blocks per group that make pairgram_wide_kernel's grid about
+// kWideBlocks blocks (grid_groups aims for 4096)
+int wide_group_blocks(int NT) { return NT * (4096 / kWideBlocks); }
 
 template <bool MUL>
 int launch_diff(const char* what, const float* const* d_src, int32_t K, const float* d_ref, const float* d_c, int64_t N,
@@ -1160,6 +1393,11 @@ int64_t fedagg_robust_work_len(int32_t kind, int32_t K, int64_t n_chunks) {
     if (K <= kTriMax) return int64_t(16) * tri_blocks(K) * grid_groups(4, n_chunks, 0, 0);
     const int NT = pair_tiles(K);
     return int64_t(NT) * grid_groups(NT, n_chunks, 0, 0) * (kPT * kPT);
+  }
+  if (kind == FEDAGG_WORK_PAIRGRAM_WIDE) {
+    if (K > kWideMax) return -1;
+    const int NT = pair_tiles(K);
+    return int64_t(NT) * grid_groups(wide_group_blocks(NT), n_chunks, 0, 0) * (kPT * kPT) + int64_t(K) * K;
   }
   if (kind == FEDAGG_WORK_WSUM_DIST2) return fedagg_wsum_dist2_work_len_internal(K, n_chunks);  // geomed.hip
   return -1;
@@ -1252,6 +1490,33 @@ int fedagg_pairgram2_f32(const float* const* d_src, int32_t K, const int64_t* d_
   hipLaunchKernelGGL(gram_sum_kernel, dim3(unsigned((per + 63) / 64)), dim3(256), 0, st, d_work, G, K, M);
   hipLaunchKernelGGL(gram_dist_kernel, dim3(unsigned((mat + 255) / 256)), dim3(256), 0, st, M, K, d_out);
   return check_launch("fedagg_pairgram2_f32");
+}
+
+int fedagg_pairgram2_wide_f32(const float* const* d_src, int32_t K, const float* d_center, const int64_t* d_chunks,
+                              int64_t n_chunks, double* d_out, double* d_work, int64_t work_len,
+                              fedagg_stream_t stream) {
+  if (K < 1 || K > kWideMax || n_chunks < 0)
+    return set_error(FEDAGG_EINVAL, "fedagg_pairgram2_wide_f32: K must be in [1, 1024] and n_chunks >= 0");
+  if (!d_src || !d_center || !d_out || (n_chunks > 0 && (!d_chunks || !d_work)))
+    return set_error(FEDAGG_EINVAL, "fedagg_pairgram2_wide_f32: null pointer");
+  const int NT = pair_tiles(K);
+  const int64_t per = int64_t(NT) * kPT * kPT;
+  const int64_t mat = int64_t(K) * K;
+  if (n_chunks > 0 && work_len < per + mat)
+    return set_error(FEDAGG_EINVAL, "fedagg_pairgram2_wide_f32: workspace too small (fedagg_robust_work_len)");
+  auto st = static_cast<hipStream_t>(stream);
+  if (n_chunks == 0) {
+    if (hipMemsetAsync(d_out, 0, sizeof(double) * K * K, st) != hipSuccess)
+      return check_launch("fedagg_pairgram2_wide_f32");
+    return FEDAGG_OK;
+  }
+  const int G = grid_groups(wide_group_blocks(NT), n_chunks, work_len - mat, per);
+  double* M = d_work + int64_t(G) * per;
+  hipLaunchKernelGGL(pairgram_wide_kernel, dim3(unsigned(NT), unsigned(G)), dim3(kWideBS), 0, st, d_src, K, d_center,
+                     d_chunks, n_chunks, G, d_work);
+  hipLaunchKernelGGL(gram_wide_sum_kernel, dim3(unsigned(per / 64)), dim3(256), 0, st, d_work, G, K, M);
+  hipLaunchKernelGGL(gram_dist_kernel, dim3(unsigned((mat + 255) / 256)), dim3(256), 0, st, M, K, d_out);
+  return check_launch("fedagg_pairgram2_wide_f32");
 }
 
 int fedagg_clip_diff_f32(const float* const* d_src, int32_t K, const float* d_ref, const float* d_div, int64_t N,

@@ -53,7 +53,11 @@ that are pure reductions over the client axis.
                 2018) under our own name and our own specification.  Stage 1
                 picks theta = K - 2f clients by repeated Krum on the K x K
                 squared distances of the weight keys (pairdist2_rows, computed
-                once; the rounds re-score on the host, bulyan_select).  Stage
+                once: the Gram on the matrix cores up to 128 clients, its
+                tile-pair form fedagg_pairgram2_wide_f32 from 129 to 1024 in
+                the tiers of PAIRGRAM_WIDE_AUTO, the exact kernel when
+                gram_condition says so or above 1024; the rounds re-score on
+                the host, bulyan_select).  Stage
                 2 averages, per coordinate of EVERY key, the beta = theta - 2f
                 selected values nearest the coordinate's median
                 (fedagg_nearmedian_mean_f32, specified in include/fedagg.h:
@@ -65,10 +69,13 @@ that are pure reductions over the client axis.
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
                 the K x K squared distances of the clients' weight vectors are
-                one fedagg_pairdist2_f32 launch; the scores (sum of the
-                K - f - 2 smallest), their fp32 argsort and the returned
-                sub-list of the ORIGINAL (sample_num, dict) tuples follow the
-                reference on the host (K numbers).
+                one pairdist2_rows call (fedagg_pairdist2_f32, or by default
+                the centred Gram on the matrix cores: fedagg_pairgram2_f32 up
+                to 128 clients, fedagg_pairgram2_wide_f32 from 129 to 1024);
+                the scores (sum of the K - f - 2 smallest; in numpy above 128
+                clients, bit for bit the reference's loop), their fp32 argsort
+                and the returned sub-list of the ORIGINAL (sample_num, dict)
+                tuples follow the reference on the host (K numbers).
 
 "slsgd"         SLSGDDefense (slsgd_defense.py:28-67): option 2 trims by
                 sample count before aggregation (the trimmed-mean helper);
@@ -531,29 +538,89 @@ def gram_condition(D: np.ndarray) -> float:
     return m if np.isfinite(m) else float("inf")
 
 
+# fedagg_pairgram2_wide_f32 holds up to 1024 clients (csrc/robust.hip)
+PAIRGRAM_WIDE_MAX_CLIENTS = nat.PAIRGRAM_WIDE_MAX_CLIENTS
+# The K tiers (K <= tier) in which pairdist2_rows' "auto" runs "gram_wide"
+# above 128 clients: those where its median time, the centre pass included,
+# beat the exact kernel's by more than the larger min-max spread of the two
+# (TRIMMED_WIDE_AUTO's rule; tools/pairgram_wide_probe.py ->
+# profiles/pairgram_wide_probe.json, NOTES.md §5c).  A tier that
+# did not win stays False and "auto" keeps the exact kernel there.  Measured
+# at 4,194,304 fp32 columns, both launched alternately on the same rows,
+# median of 10 (min - max), exact / gram_wide; a tier is True when its full K
+# and its padded K both pass  gap = exact - gram_wide > larger spread:
+#   tier  256: K = 256  8.06 (8.01 - 8.26) / 4.06 (4.03 - 4.10) ms: gap 4.00 > 0.26;
+#              K = 200  7.76 (7.72 - 7.84) / 3.95 (3.86 - 3.98): gap 3.81 > 0.13
+#   tier  512: K = 512  29.74 (29.60 - 29.92) / 14.37 (14.30 - 14.45): gap 15.37 > 0.32;
+#              K = 384  17.59 (17.40 - 17.71) / 8.44 (8.41 - 8.49): gap 9.15 > 0.30
+#   tier 1024: K = 1024 111.53 (111.09 - 111.61) / 50.74 (50.41 - 51.37): gap 60.79 > 0.96;
+#              K = 700  54.61 (54.10 - 54.96) / 25.52 (25.39 - 25.65): gap 29.09 > 0.86
+# (2.0x - 2.2x; the centre pass, 0.5 - 2.6 ms, is inside gram_wide's time.)
+PAIRGRAM_WIDE_AUTO = {256: True, 512: True, 1024: True}
+
+
+def pairgram_wide_auto(K: int) -> bool:
+    """Whether pairdist2_rows' "auto" runs the wide Gram for K clients above
+    GRAM_MAX_CLIENTS (PAIRGRAM_WIDE_AUTO)."""
+    return _tier_auto(PAIRGRAM_WIDE_AUTO, PAIRGRAM_WIDE_MAX_CLIENTS, K)
+
+
+def client_mean_row(d_ptrs: torch.Tensor, K: int, length: int, device, aligned: bool = False) -> torch.Tensor:
+    """The mean of K fp32 device rows over their first `length` columns: one
+    pass of the FedAvg kernel with device weights 1/K (the wide Gram's centre).
+    aligned: every row is 16-byte aligned (the kernel's vector path)."""
+    out = torch.empty(max(length, 1), dtype=torch.float32, device=device)
+    d_w = torch.full((K,), 1.0 / K, dtype=torch.float32, device=device)
+    kn.wsum_ptrs(torch.float32, d_ptrs, d_w, K, length, out, aligned)
+    return out
+
+
 def pairdist2_rows(d_ptrs: torch.Tensor, K: int, chunks: torch.Tensor, n_chunks: int, device,
-                   method: str = "auto") -> torch.Tensor:
+                   method: str = "auto", *, length: "int | None" = None,
+                   center: "torch.Tensor | None" = None, aligned: bool = False) -> torch.Tensor:
     """K x K fp64 squared distances of K fp32 device rows over the chunked
     columns.  method "exact": the reference's fp32 differences, squared and
     summed on the VALU (fedagg_pairdist2_f32); "gram": the centred Gram on the
     bf16 matrix cores with an exact three-way split (fedagg_pairgram2_f32,
-    K <= 128); "auto": gram when K allows it (same Krum
-    selections, ~3x faster at config 3)
+    K <= 128); "gram_wide": the same Gram by 64-client tile pairs
+    (fedagg_pairgram2_wide_f32, K <= 1024), centred on `center`, an fp32 device
+    row indexed like the client rows, or, when center is None, on the mean of
+    the rows' first `length` columns (client_mean_row; length must then cover
+    every chunk; aligned: the rows are 16-byte aligned, as bucket rows are, so
+    that pass takes its vector path); "auto": gram when K allows it (same Krum
+    selections, ~3x faster at config 3), gram_wide above 128 clients in the
+    tiers of PAIRGRAM_WIDE_AUTO when a length or a centre is given,
     and the result is well conditioned (``gram_condition`` <=
     GRAM_MAX_CONDITION), else the exact kernel: one far-away update (the case
     Krum exists for) moves the client mean, and the honest clients' distances
     would then carry the Gram's error scaled by that update's norm."""
-    if method not in ("auto", "gram", "exact"):
-        raise ValueError(f"pair distance method {method!r}: 'auto', 'gram' or 'exact'")
+    if method not in ("auto", "gram", "gram_wide", "exact"):
+        raise ValueError(f"pair distance method {method!r}: 'auto', 'gram', 'gram_wide' or 'exact'")
     gram = method == "gram" or (method == "auto" and K <= GRAM_MAX_CLIENTS)
     if gram and K > GRAM_MAX_CLIENTS:
         raise ValueError(f"the Gram pair kernel holds at most {GRAM_MAX_CLIENTS} clients (K = {K})")
+    wide = method == "gram_wide" or (method == "auto" and not gram and pairgram_wide_auto(K)
+                                     and (length is not None or center is not None))
+    if wide and K > PAIRGRAM_WIDE_MAX_CLIENTS:
+        raise ValueError(f"the wide Gram pair kernel holds at most {PAIRGRAM_WIDE_MAX_CLIENTS} clients (K = {K})")
+    if wide and center is None and length is None:
+        raise ValueError("pair distance method 'gram_wide' needs the rows' length or a centre row")
     out = torch.empty((K, K), dtype=torch.float64, device=device)
-    work = _work(nat.WORK_PAIRGRAM if gram else nat.WORK_PAIRDIST2, K, n_chunks, device)
-    fn = nat.lib().fedagg_pairgram2_f32 if gram else nat.lib().fedagg_pairdist2_f32
-    nat.check(fn(d_ptrs.data_ptr(), K, chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(), work.numel(),
-                 nat.stream_handle()), "pairgram2" if gram else "pairdist2")
-    if gram and method == "auto" and gram_condition(out.cpu().numpy()) > GRAM_MAX_CONDITION:
+    if wide:
+        if center is None:
+            center = client_mean_row(d_ptrs, K, length, device, aligned)
+        elif center.dtype != torch.float32 or not center.is_cuda:
+            raise TypeError("pair distance centre: an fp32 device row")
+        work = _work(nat.WORK_PAIRGRAM_WIDE, K, n_chunks, device)
+        nat.check(nat.lib().fedagg_pairgram2_wide_f32(d_ptrs.data_ptr(), K, center.data_ptr(), chunks.data_ptr(),
+                                                      n_chunks, out.data_ptr(), work.data_ptr(), work.numel(),
+                                                      nat.stream_handle()), "pairgram2_wide")
+    else:
+        work = _work(nat.WORK_PAIRGRAM if gram else nat.WORK_PAIRDIST2, K, n_chunks, device)
+        fn = nat.lib().fedagg_pairgram2_f32 if gram else nat.lib().fedagg_pairdist2_f32
+        nat.check(fn(d_ptrs.data_ptr(), K, chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(), work.numel(),
+                     nat.stream_handle()), "pairgram2" if gram else "pairdist2")
+    if (gram or wide) and method == "auto" and gram_condition(out.cpu().numpy()) > GRAM_MAX_CONDITION:
         return pairdist2_rows(d_ptrs, K, chunks, n_chunks, device, "exact")
     return out
 
@@ -605,12 +672,49 @@ def krum_scores(D: np.ndarray, byzantine_client_num: int) -> list:
     squared distances: each distance enters as the reference's
     `norm.item() ** 2`, the K - f - 2 smallest are summed in ascending order."""
     K = D.shape[0]
+    if K > KRUM_SCORES_LOOP_MAX_CLIENTS:
+        scores = krum_scores_numpy(D, byzantine_client_num)
+        if scores is not None:
+            return scores
+    return krum_scores_loop(D, byzantine_client_num)
+
+
+# krum_scores runs its Python double loop up to this many clients and numpy
+# above: the loop makes K (K - 1) fp32_norm calls, about a million (seconds)
+# at K = 1024, beside a distance kernel that takes milliseconds
+KRUM_SCORES_LOOP_MAX_CLIENTS = 128
+
+
+def krum_scores_loop(D: np.ndarray, byzantine_client_num: int) -> list:
+    """krum_scores as the reference writes it: the path up to
+    KRUM_SCORES_LOOP_MAX_CLIENTS clients and the reference of the numpy form."""
+    K = D.shape[0]
     scores = []
     for i in range(K):
         dists = [fp32_norm(D[i, j]) ** 2 for j in range(K) if j != i]
         dists.sort()
         scores.append(sum(dists[0:K - byzantine_client_num - 2]))
     return scores
+
+
+def krum_scores_numpy(D: np.ndarray, byzantine_client_num: int) -> "list | None":
+    """krum_scores_loop's scores, bit for bit, in numpy: the fp32 root, its
+    square in float64 (exact: 24 x 24 bits), each row without its diagonal
+    entry sorted, and the first K - f - 2 added one after the other in
+    ascending order (cumsum adds sequentially, as sum() over the list does).
+    None when a root is NaN (a NaN or negative entry): list.sort() and np.sort
+    place NaN differently, so the loop decides those."""
+    K = D.shape[0]
+    with np.errstate(invalid="ignore"):
+        R = np.sqrt(np.asarray(D, dtype=np.float64)).astype(np.float32).astype(np.float64)
+    if np.isnan(R).any():
+        return None
+    R = (R * R)[~np.eye(K, dtype=bool)].reshape(K, K - 1)
+    R.sort(axis=1)
+    head = R[:, 0:K - byzantine_client_num - 2]  # the list slice's semantics, negative counts included
+    if head.shape[1] == 0:
+        return [0] * K
+    return np.cumsum(head, axis=1)[:, -1].tolist()
 
 
 def krum_before_aggregation(raw_client_grad_list: Sequence, byzantine_client_num: int, krum_param_m: int = 1,
@@ -625,7 +729,8 @@ def krum_before_aggregation(raw_client_grad_list: Sequence, byzantine_client_num
     bucket, g, _, dev = _weight_bucket([item[1] for item in raw_client_grad_list], "krum", device)
     with torch.cuda.device(dev):
         chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
-        D = pairdist2_rows(g.d_ptrs, num_client, chunks, n_chunks, dev, method).cpu().numpy()
+        D = pairdist2_rows(g.d_ptrs, num_client, chunks, n_chunks, dev, method, length=g.length,
+                           aligned=True).cpu().numpy()
     scores = krum_scores(D, byzantine_client_num)
     score_index = torch.argsort(torch.Tensor(scores)).tolist()[0:krum_param_m]
     return [raw_client_grad_list[i] for i in score_index]
@@ -1452,8 +1557,8 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
         raise ValueError("bulyan: byzantine_client_num must be >= 0")
     if K < 4 * f + 3:
         raise ValueError(f"bulyan: byzantine_client_num = {f} needs at least 4f + 3 = {4 * f + 3} clients (got {K})")
-    if method not in ("auto", "gram", "exact"):
-        raise ValueError(f"pair distance method {method!r}: 'auto', 'gram' or 'exact'")
+    if method not in ("auto", "gram", "gram_wide", "exact"):
+        raise ValueError(f"pair distance method {method!r}: 'auto', 'gram', 'gram_wide' or 'exact'")
     theta, beta = K - 2 * f, K - 4 * f
     dicts, keys = _client_dicts(raw_client_grad_list)
     if not keys:
@@ -1471,7 +1576,8 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
             selected, scores = bulyan_select(np.empty((K, 0)), 0)  # no distances needed
         else:
             chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
-            D = pairdist2_rows(g.d_ptrs, K, chunks, n_chunks, dev, method).cpu().numpy()
+            D = pairdist2_rows(g.d_ptrs, K, chunks, n_chunks, dev, method, length=g.length,
+                               aligned=True).cpu().numpy()
             selected, scores = bulyan_select(D, f)
         if theta <= NEARMEDIAN_MAX_CLIENTS or nearmedian_wide_auto(theta):
             ptrs = g.d_ptrs if selected == list(range(K)) else \

@@ -529,6 +529,39 @@ int fedagg_pairgram2_f32(const float* const* d_src, int32_t K,
                          const int64_t* d_chunks, int64_t n_chunks, double* d_out,
                          double* d_work, int64_t work_len, fedagg_stream_t stream);
 
+/* The same K x K matrix for 1 <= K <= FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS, by
+ * the same split Gram (c = h + m + l, the six bf16 MFMA products, fp32 over 4
+ * stages, fp64 across) in a form whose blocks hold one pair of 64-client
+ * tiles, not every client: the pair matrix is cut as fedagg_pairdist2_f32
+ * cuts it above 128 clients and each block runs the Gram's inner loop on its
+ * tile pair.  No block sees all K rows, so the centre is an argument:
+ *   c_i[e] = fl32(src_i[e] - d_center[e]),   G = C C^T,
+ *   d_out[i*K + j] = max(0, G_ii + G_jj - (G_ij + G_ji)).
+ * d_center is one fp32 device row indexed by absolute column like the client
+ * rows (any alignment; only the table's columns are read); it must not be
+ * null.  D is translation invariant, so every centre is correct and the
+ * centre only decides conditioning: |error| ~ 1e-7 (|c_i|^2 + |c_j|^2) with
+ * the norms taken about the centre used.  Callers pass the client mean (one
+ * fedagg_wsum_f32 pass with weights 1/K), which makes the bound
+ * fedagg_pairgram2_f32's.  Guarantees as there: d_out is exactly symmetric, 0
+ * on the diagonal, never negative, and NaN / inf pass through (an inf or NaN
+ * element, or squares beyond fp32, make that client's row and column
+ * non-finite).  Deterministic: per-block partials in d_work, combined in a
+ * fixed order.  d_work: fedagg_robust_work_len(FEDAGG_WORK_PAIRGRAM_WIDE, K,
+ * n_chunks) doubles (-1 there for K > 1024); a smaller one is accepted down to
+ * one chunk group's 4,096 doubles per 64 x 64 tile pair plus the K x K matrix
+ * and runs fewer chunk groups, as described above.  n_chunks == 0: d_out = 0.
+ * Stream-ordered; allocates nothing and does not synchronise.  FEDAGG_EINVAL
+ * (checked before any HIP call) for K < 1, K > 1024, n_chunks < 0, a null
+ * d_src, d_center or d_out, a null d_chunks or d_work with n_chunks > 0, or a
+ * workspace below that minimum. */
+#define FEDAGG_WORK_PAIRGRAM_WIDE 4
+#define FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS 1024
+int fedagg_pairgram2_wide_f32(const float* const* d_src, int32_t K,
+                              const float* d_center, const int64_t* d_chunks,
+                              int64_t n_chunks, double* d_out, double* d_work,
+                              int64_t work_len, fedagg_stream_t stream);
+
 /* One Weiszfeld iteration of the geometric-median defense ("geomed";
  * csrc/geomed.hip) in ONE pass over the K fp32 rows: the weighted sum z of
  * the rows and every row's squared distance to z.  Only the columns of the
