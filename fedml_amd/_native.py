@@ -68,6 +68,7 @@ SIGNATURES = {
     "fedagg_sum": (ctypes.c_int, [_I32, _P, _I32, _I64, _P, _U32, _P]),
     "fedagg_wsum_muldiv": (ctypes.c_int, [_I32, _P, _P, _I32, _I64, _P, _U32, _P]),
     "fedagg_multi_blocks": (_I64, [_I32, _I64]),
+    "fedagg_epi_tile": (_I32, [_I32, _I64]),
     "fedagg_wsum_multi_f32": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _I64, _P]),
     "fedagg_wsum_multi": (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, _I64, _P]),
     "fedagg_fedopt_sgd_f32": (ctypes.c_int, [_P, _P, _P, _I64, _F, _F, _I32, _P]),

@@ -1202,6 +1202,16 @@ int64_t blocks_for(int64_t numel) {
   return (packs + per - 1) / per;
 }
 
+// The tile launch_epi and launch_fused give a tensor of `blocks` shipped blocks
+// (fedagg_epi_tile reports it).
+enum : int32_t { kTileSmall = 0, kTileMid2 = 1, kTileMid = 2, kTileCfg = 3 };
+inline int32_t tile_for_blocks(int64_t blocks) {
+  if (blocks < kSmallBelowBlocks) return kTileSmall;
+  if (blocks < kMid2BelowBlocks) return kTileMid2;
+  if (blocks <= kMidUpToBlocks) return kTileMid;
+  return kTileCfg;
+}
+
 template <class OP, int U, int V, bool NT, int BS = 256, class WS = PtrW<typename OP::w_t>>
 int launch_uvn(const typename OP::in_t* const* src, const WS& w, int32_t K, int64_t N, typename OP::out_t* out,
                bool aligned, hipStream_t stream, const char* name) {
@@ -1301,17 +1311,20 @@ int launch_epi_cfg(const Seg<OP>& s, const EPI& epi, const WS& w, int32_t K, boo
 template <class OP, class EPI, class WS>
 int launch_epi(const Seg<OP>& s, const EPI& epi, const WS& w, int32_t K, bool aligned, hipStream_t st,
                const char* name) {
-  const int64_t blocks = blocks_for<OP>(s.numel);
-  if (blocks < kSmallBelowBlocks)
-    return launch_epi_cfg<OP, EPI, WS, SmallCfg::U, SmallCfg::V, SmallCfg::NT, SmallCfg::BS>(s, epi, w, K, aligned,
-                                                                                            st, name);
-  if (blocks < kMid2BelowBlocks)
-    return launch_epi_cfg<OP, EPI, WS, Mid2Cfg::U, Mid2Cfg::V, Mid2Cfg::NT, Mid2Cfg::BS>(s, epi, w, K, aligned, st,
-                                                                                        name);
-  if (blocks <= kMidUpToBlocks)
-    return launch_epi_cfg<OP, EPI, WS, MidCfg::U, MidCfg::V, MidCfg::NT, MidCfg::BS>(s, epi, w, K, aligned, st, name);
-  return launch_epi_cfg<OP, EPI, WS, Cfg<OP>::U, Cfg<OP>::V, Cfg<OP>::NT, Cfg<OP>::BS>(s, epi, w, K, aligned, st,
+  switch (tile_for_blocks(blocks_for<OP>(s.numel))) {
+    case kTileSmall:
+      return launch_epi_cfg<OP, EPI, WS, SmallCfg::U, SmallCfg::V, SmallCfg::NT, SmallCfg::BS>(s, epi, w, K, aligned,
+                                                                                              st, name);
+    case kTileMid2:
+      return launch_epi_cfg<OP, EPI, WS, Mid2Cfg::U, Mid2Cfg::V, Mid2Cfg::NT, Mid2Cfg::BS>(s, epi, w, K, aligned, st,
+                                                                                          name);
+    case kTileMid:
+      return launch_epi_cfg<OP, EPI, WS, MidCfg::U, MidCfg::V, MidCfg::NT, MidCfg::BS>(s, epi, w, K, aligned, st,
                                                                                       name);
+    default:
+      return launch_epi_cfg<OP, EPI, WS, Cfg<OP>::U, Cfg<OP>::V, Cfg<OP>::NT, Cfg<OP>::BS>(s, epi, w, K, aligned, st,
+                                                                                          name);
+  }
 }
 
 // Weights passed in the kernel arguments (flags & FEDAGG_HOST_WEIGHTS): w is a
@@ -1977,18 +1990,15 @@ void launch_fused_cfg(const Seg<OpF32>& s, const EPI& epi, const WS& w, int32_t 
 
 template <bool FUSED_CAP, class EPI, class WS>
 void launch_fused(const Seg<OpF32>& s, const EPI& epi, const WS& w, int32_t K, bool aligned, hipStream_t st) {
-  const int64_t blocks = blocks_for<OpF32>(s.numel);
   // A device's shard of a one-process multi-GPU FedOpt round (config 5 over 8
   // GPUs: 16 keys, 524,288 elements) is 128 mid tiles: half the CUs.  The
   // plain FedAvg tiers apply (§6a).
-  if (blocks < kSmallBelowBlocks)
-    launch_fused_cfg<FUSED_CAP, SmallCfg>(s, epi, w, K, aligned, st);
-  else if (blocks < kMid2BelowBlocks)
-    launch_fused_cfg<FUSED_CAP, Mid2Cfg>(s, epi, w, K, aligned, st);
-  else if (blocks <= kMidUpToBlocks)
-    launch_fused_cfg<FUSED_CAP, MidCfg>(s, epi, w, K, aligned, st);
-  else
-    launch_fused_cfg<FUSED_CAP, Cfg<OpF32>>(s, epi, w, K, aligned, st);
+  switch (tile_for_blocks(blocks_for<OpF32>(s.numel))) {
+    case kTileSmall: launch_fused_cfg<FUSED_CAP, SmallCfg>(s, epi, w, K, aligned, st); break;
+    case kTileMid2: launch_fused_cfg<FUSED_CAP, Mid2Cfg>(s, epi, w, K, aligned, st); break;
+    case kTileMid: launch_fused_cfg<FUSED_CAP, MidCfg>(s, epi, w, K, aligned, st); break;
+    default: launch_fused_cfg<FUSED_CAP, Cfg<OpF32>>(s, epi, w, K, aligned, st); break;
+  }
 }
 
 template <class OP>
@@ -2120,6 +2130,15 @@ int64_t fedagg_multi_blocks(int32_t dtype, int64_t numel) {
   }
 }
 
+int32_t fedagg_epi_tile(int32_t elem_bytes, int64_t N) {
+  if (N < 0) return -1;
+  switch (elem_bytes) {
+    case 2: return tile_for_blocks(blocks_for<OpBF16MulDiv>(N));
+    case 4: return tile_for_blocks(blocks_for<OpF32>(N));
+    case 8: return tile_for_blocks(blocks_for<OpF64MulDiv>(N));
+    default: return -1;
+  }
+}
 
 int fedagg_wsum_multi(int32_t dtype, int32_t acc_mode, const void* const* d_src, void* const* d_out,
                       const int64_t* d_numel, const int64_t* d_block_begin, int32_t T, const float* d_w, int32_t K,

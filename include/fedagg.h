@@ -133,6 +133,14 @@ int fedagg_sum(int32_t dtype, const void* const* d_src, int32_t K, int64_t N,
  * fedagg_wsum_multi takes FEDAGG_DT_F32, _BF16, _F16 (acc_mode as for
  * fedagg_wsum_bf16; outputs keep the dtype) or _I64 (float32 outputs). */
 int64_t fedagg_multi_blocks(int32_t dtype, int64_t numel);
+/* Host only: the tile configuration that the launches with an epilogue
+ * (fedagg_wsum_rlr_f32, fedagg_wsum_muldiv, fedagg_sum_mod_i64,
+ * fedagg_lsa_reconstruct_f32 and every fedagg_wsum_fedopt_*) give N elements
+ * of elem_bytes (2, 4 or 8) each: 0 small (64 lanes, one 16-byte pack per
+ * lane, 16 clients in flight), 1 / 2 / 3 the 256-lane tiles of four packs per
+ * lane with 2 / 1 / 4 clients in flight.  -1 for another element size or
+ * N < 0.  For tests and tools that must know which launch a size reaches. */
+int32_t fedagg_epi_tile(int32_t elem_bytes, int64_t N);
 int fedagg_wsum_multi(int32_t dtype, int32_t acc_mode, const void* const* d_src,
                       void* const* d_out, const int64_t* d_numel,
                       const int64_t* d_block_begin, int32_t T, const float* d_w,
