@@ -27,6 +27,8 @@ DT_F32, DT_BF16, DT_F16, DT_F64, DT_I64, DT_I32 = 0, 1, 2, 3, 4, 5
 DIST_CHUNK, PAIR_CHUNK = 1024, 256  # FEDAGG_DIST_CHUNK / FEDAGG_PAIR_CHUNK
 WORK_DIST2, WORK_PAIRDIST2, WORK_PAIRGRAM, WORK_WSUM_DIST2 = 0, 1, 2, 3
 WORK_PAIRGRAM_WIDE = 4  # FEDAGG_WORK_PAIRGRAM_WIDE
+WORK_DOTNORM2 = 5  # FEDAGG_WORK_DOTNORM2
+WSUM_DIFF_TILE = 2048  # FEDAGG_WSUM_DIFF_TILE: columns a block of fedagg_wsum_diff_f32 works at a time
 PAIRGRAM_WIDE_MAX_CLIENTS = 1024  # FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS
 TRIMMED_MAX_CLIENTS = 128  # FEDAGG_TRIMMED_MAX_CLIENTS
 TRIMMED_WIDE_MAX_CLIENTS = 1024  # FEDAGG_TRIMMED_WIDE_MAX_CLIENTS
@@ -105,6 +107,8 @@ SIGNATURES = {
     "fedagg_pairgram2_wide_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_clip_diff_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "fedagg_scale_diff_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
+    "fedagg_dotnorm2_f32": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),
+    "fedagg_wsum_diff_f32": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _P]),
     "fedagg_last_error": (ctypes.c_char_p, []),
     "fedagg_version": (_I32, []),
 }

@@ -16,6 +16,8 @@
 //   fedagg_pairdist2_f32 out[i][j] = sum_e (x_i[e] - x_j[e])^2   (VALU-bound, packed fp32)
 //   fedagg_clip_diff_f32 y_i[e] = fl(fl(fl(x_i[e] - r[e]) / c_i) + r[e])
 //   fedagg_scale_diff_f32 y_i[e] = fl(fl(x_i[e] - r[e]) * s_i)   (CClip)
+//   fedagg_dotnorm2_f32  out[i] = sum_e (x_i[e] - r[e]) (d[e] - r[e]), out[K + i] = sum_e (x_i[e] - r[e])^2
+//   fedagg_wsum_diff_f32 y[e] = fl(r[e] + chain_i fl(c_i * fl(x_i[e] - r[e])))   (both: FLTrust, ours)
 //
 // Every difference is the fp32 difference the reference forms
 // (vec_local - vec_global, v1 - v2).  dist2 squares it exactly in fp64 and sums
@@ -159,6 +161,83 @@ __global__ __launch_bounds__(kBS) void dist2_kernel(const float* const* __restri
       if (i < K) {
         const double t = wave_sum(acc[j]);
         if (lane == 0) partial[int64_t(i) * G + g] = t;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// FLTrust's cosines: per client the dot product of a_i = x_i - ref with
+// b = dir - ref and |a_i|^2, in ONE pass over the rows.  dist2_kernel's shape:
+// a block owns the chunks g, g + G, ... for every client, each lane holds its
+// ref columns AND its b columns (the fp32 difference, formed once per chunk)
+// in registers, and wave w streams clients w, w + 4, ... against them with two
+// fp64 accumulators per client.  Both products of fp32 values are exact in
+// fp64, so each sum is the exact sum up to fp64 rounding, as dist2's.
+// Partials are laid out [2K][G] (dots, then squared norms): sum_rows_kernel
+// finishes them with 2K blocks.
+//
+// Clients per wave per pass: twice dist2's accumulators plus b sit in
+// registers, so the batch is dist2's question again (kBatch's note) with more
+// at stake.  FEDAGG_DOTNORM_BATCH builds the other size for
+// tools/fltrust_probe.py; the measured pair is in NOTES.md §7c.
+#ifndef FEDAGG_DOTNORM_BATCH
+#define FEDAGG_DOTNORM_BATCH 8
+#endif
+constexpr int kDotBatch = FEDAGG_DOTNORM_BATCH;
+// 8 clients fit 4 waves per SIMD when the compiler is held to it (119 VGPRs,
+// no spill; 135 and 3 waves when it is not), which is what the grid of 1,024
+// blocks needs to be resident at once; 16 clients need 159 and spill under
+// that cap, so they run at 3
+constexpr int kDotWavesPerSimd = kDotBatch <= 8 ? 4 : 3;
+
+__device__ __forceinline__ void dot_norm(float x, float r, float b, double& dot, double& nrm) {
+  const double a = double(x - r);  // the fp32 difference, widened
+  dot = __builtin_fma(a, double(b), dot);  // exact products, fp64 sums
+  nrm = __builtin_fma(a, a, nrm);
+}
+
+__global__ __launch_bounds__(kBS, kDotWavesPerSimd) void dotnorm2_kernel(
+    const float* const* __restrict__ src, int K, const float* __restrict__ ref, const float* __restrict__ dir,
+    const int64_t* __restrict__ chunks, int64_t n_chunks, int G, double* __restrict__ partial) {
+  const int g = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int cb = 0; cb < K; cb += kWaves * kDotBatch) {
+    double dot[kDotBatch], nrm[kDotBatch];
+#pragma unroll
+    for (int j = 0; j < kDotBatch; ++j) dot[j] = nrm[j] = 0.0;
+    for (int64_t c = g; c < n_chunks; c += G) {
+      const int64_t start = chunks[2 * c];
+      const int len = int(chunks[2 * c + 1]);
+      f32x4 r[kLaneCols / 4], b[kLaneCols / 4];
+      load_chunk<false>(ref + start, len, lane, r);
+      load_chunk<false>(dir + start, len, lane, b);
+#pragma unroll
+      for (int u = 0; u < kLaneCols / 4; ++u) b[u] = b[u] - r[u];  // columns past len: 0 - 0
+#pragma unroll
+      for (int j = 0; j < kDotBatch; ++j) {
+        const int i = cb + w + kWaves * j;
+        if (i < K) {  // wave-uniform
+          f32x4 x[kLaneCols / 4];
+          load_chunk<true>(src[i] + start, len, lane, x);
+#pragma unroll
+          for (int u = 0; u < kLaneCols / 4; ++u) {
+            dot_norm(x[u].x, r[u].x, b[u].x, dot[j], nrm[j]);
+            dot_norm(x[u].y, r[u].y, b[u].y, dot[j], nrm[j]);
+            dot_norm(x[u].z, r[u].z, b[u].z, dot[j], nrm[j]);
+            dot_norm(x[u].w, r[u].w, b[u].w, dot[j], nrm[j]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kDotBatch; ++j) {
+      const int i = cb + w + kWaves * j;
+      if (i < K) {
+        const double td = wave_sum(dot[j]), tn = wave_sum(nrm[j]);
+        if (lane == 0) {
+          partial[int64_t(i) * G + g] = td;
+          partial[(int64_t(K) + i) * G + g] = tn;
+        }
       }
     }
   }
@@ -1346,6 +1425,106 @@ __global__ __launch_bounds__(kBS) void clip_diff_kernel(const float* const* __re
 
 constexpr int kClipClients = 2;  // clients in flight per wave in clip_diff_kernel
 
+// ---------------------------------------------------------------------------
+// FLTrust's rebuild: out = ref + sum_i c_i (x_i - ref) as the fp32 chain
+//   acc = fl(c_0 * fl(x_0 - ref)); acc = fl(acc + fl(c_i * fl(x_i - ref))); out = fl(ref + acc)
+// (K == 0: out = ref).  A streaming kernel: every byte is read once, so all
+// loads are non-temporal.  A block owns tiles of FEDAGG_WSUM_DIFF_TILE columns,
+// a thread kWdVec f32x4 columns of each (1,024 columns apart: a wave's load is
+// 1 KB contiguous); it loads ref once, then walks the clients kWdClients at a
+// time, all their loads issued before the first use (kWdClients * kWdVec
+// 16-byte loads in flight per lane).  c_i is wave-uniform.  A row (and ref,
+// and out) takes 16-byte accesses when its pointer is 16-byte aligned and the
+// tile lies whole inside N, 4-byte accesses otherwise: the row pointers live
+// in device memory, so the choice is made per pointer here (wave-uniform), not
+// on the host.
+constexpr int kWdVec = 2;
+constexpr int kWdClients = 4;
+constexpr int kWdTile = FEDAGG_WSUM_DIFF_TILE;
+static_assert(kWdTile == kBS * 4 * kWdVec, "FEDAGG_WSUM_DIFF_TILE is the block's columns per tile");
+
+// the thread's f32x4 at column `col` of a row of N columns; columns past N read 0
+__device__ __forceinline__ f32x4 wd_load(const float* p, int64_t col, int64_t N, bool vec) {
+  if (vec) return ld4<true>(p + col);
+  f32x4 v;
+  v.x = col < N ? __builtin_nontemporal_load(gptr(p) + col) : 0.f;
+  v.y = col + 1 < N ? __builtin_nontemporal_load(gptr(p) + col + 1) : 0.f;
+  v.z = col + 2 < N ? __builtin_nontemporal_load(gptr(p) + col + 2) : 0.f;
+  v.w = col + 3 < N ? __builtin_nontemporal_load(gptr(p) + col + 3) : 0.f;
+  return v;
+}
+
+__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// fl(c * fl(x - r)): two roundings (the build never contracts)
+__device__ __forceinline__ f32x4 wd_term(f32x4 x, f32x4 r, float c) {
+  const f32x4 d = x - r;
+  return f32x4{d.x * c, d.y * c, d.z * c, d.w * c};
+}
+
+__global__ __launch_bounds__(kBS) void wsum_diff_kernel(const float* const* __restrict__ src,
+                                                        const float* __restrict__ cs, int K,
+                                                        const float* __restrict__ ref, int64_t N,
+                                                        float* __restrict__ out, int64_t tiles) {
+  const int t = threadIdx.x;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t base = tile * kWdTile + 4 * t;
+    const bool full = (tile + 1) * kWdTile <= N;  // block-uniform: no per-lane bounds in the tile
+    f32x4 r[kWdVec], acc[kWdVec] = {};
+    {
+      const bool vec = full && aligned16(ref);
+#pragma unroll
+      for (int u = 0; u < kWdVec; ++u) r[u] = wd_load(ref, base + 1024 * u, N, vec);
+    }
+    if (K > 0) {  // the chain starts AT client 0's term, not at 0 + it (-0 stays -0)
+      const float* p = src[0];
+      const bool vec = full && aligned16(p);
+#pragma unroll
+      for (int u = 0; u < kWdVec; ++u) acc[u] = wd_term(wd_load(p, base + 1024 * u, N, vec), r[u], cs[0]);
+    }
+    int i = 1;
+    for (; i + kWdClients <= K; i += kWdClients) {
+      f32x4 x[kWdClients][kWdVec];
+#pragma unroll
+      for (int j = 0; j < kWdClients; ++j) {
+        const float* p = src[i + j];
+        const bool vec = full && aligned16(p);
+#pragma unroll
+        for (int u = 0; u < kWdVec; ++u) x[j][u] = wd_load(p, base + 1024 * u, N, vec);
+      }
+#pragma unroll
+      for (int j = 0; j < kWdClients; ++j) {
+        const float c = cs[i + j];
+#pragma unroll
+        for (int u = 0; u < kWdVec; ++u) acc[u] = acc[u] + wd_term(x[j][u], r[u], c);
+      }
+    }
+    for (; i < K; ++i) {  // the last < kWdClients clients
+      const float* p = src[i];
+      const bool vec = full && aligned16(p);
+      const float c = cs[i];
+#pragma unroll
+      for (int u = 0; u < kWdVec; ++u) acc[u] = acc[u] + wd_term(wd_load(p, base + 1024 * u, N, vec), r[u], c);
+    }
+    const bool vec = full && aligned16(out);
+#pragma unroll
+    for (int u = 0; u < kWdVec; ++u) {
+      const f32x4 y = K > 0 ? r[u] + acc[u] : r[u];
+      const int64_t col = base + 1024 * u;
+      if (vec) {
+        __builtin_nontemporal_store(y, reinterpret_cast<f32x4*>(out + col));
+      } else {
+        if (col < N) out[col] = y.x;
+        if (col + 1 < N) out[col + 1] = y.y;
+        if (col + 2 < N) out[col + 2] = y.z;
+        if (col + 3 < N) out[col + 3] = y.w;
+      }
+    }
+  }
+}
+
+constexpr int kWdMaxBlocks = 1 << 20;  // tiles above that (N > 2^31 columns) go round the grid
+
 int grid_groups(int per_group_blocks, int64_t n_chunks, int64_t work_len, int64_t per_group_work) {
   int64_t G = (4096 + per_group_blocks - 1) / per_group_blocks;
   if (G > n_chunks) G = n_chunks;
@@ -1400,7 +1579,42 @@ int64_t fedagg_robust_work_len(int32_t kind, int32_t K, int64_t n_chunks) {
     return int64_t(NT) * grid_groups(wide_group_blocks(NT), n_chunks, 0, 0) * (kPT * kPT) + int64_t(K) * K;
   }
   if (kind == FEDAGG_WORK_WSUM_DIST2) return fedagg_wsum_dist2_work_len_internal(K, n_chunks);  // geomed.hip
+  if (kind == FEDAGG_WORK_DOTNORM2) return int64_t(2) * K * grid_groups(4, n_chunks, 0, 0);  // dist2's grid, two rows a client
   return -1;
+}
+
+int fedagg_dotnorm2_f32(const float* const* d_src, int32_t K, const float* d_ref, const float* d_dir,
+                        const int64_t* d_chunks, int64_t n_chunks, double* d_out, double* d_work, int64_t work_len,
+                        fedagg_stream_t stream) {
+  if (K < 1 || n_chunks < 0)
+    return set_error(FEDAGG_EINVAL, "fedagg_dotnorm2_f32: K must be >= 1 and n_chunks >= 0");
+  if (!d_src || !d_ref || !d_dir || !d_out || (n_chunks > 0 && (!d_chunks || !d_work)))
+    return set_error(FEDAGG_EINVAL, "fedagg_dotnorm2_f32: null pointer");
+  if (n_chunks > 0 && work_len < int64_t(2) * K)
+    return set_error(FEDAGG_EINVAL, "fedagg_dotnorm2_f32: workspace smaller than 2K doubles");
+  auto st = static_cast<hipStream_t>(stream);
+  if (n_chunks == 0) {
+    if (hipMemsetAsync(d_out, 0, sizeof(double) * 2 * K, st) != hipSuccess) return check_launch("fedagg_dotnorm2_f32");
+    return FEDAGG_OK;
+  }
+  const int G = grid_groups(4, n_chunks, work_len, int64_t(2) * K);
+  hipLaunchKernelGGL(dotnorm2_kernel, dim3(unsigned(G)), dim3(kBS), 0, st, d_src, K, d_ref, d_dir, d_chunks, n_chunks,
+                     G, d_work);
+  hipLaunchKernelGGL(sum_rows_kernel, dim3(2u * unsigned(K)), dim3(256), 0, st, d_work, G, d_out);
+  return check_launch("fedagg_dotnorm2_f32");
+}
+
+int fedagg_wsum_diff_f32(const float* const* d_src, const float* d_c, int32_t K, const float* d_ref, int64_t N,
+                         float* d_out, fedagg_stream_t stream) {
+  if (K < 0 || N < 0) return set_error(FEDAGG_EINVAL, "fedagg_wsum_diff_f32: K must be >= 0 and N >= 0");
+  if (!d_ref || !d_out || (K > 0 && (!d_src || !d_c)))
+    return set_error(FEDAGG_EINVAL, "fedagg_wsum_diff_f32: null pointer");
+  if (N == 0) return FEDAGG_OK;
+  const int64_t tiles = (N + kWdTile - 1) / kWdTile;
+  const unsigned blocks = unsigned(tiles < kWdMaxBlocks ? tiles : kWdMaxBlocks);
+  hipLaunchKernelGGL(wsum_diff_kernel, dim3(blocks), dim3(kBS), 0, static_cast<hipStream_t>(stream), d_src, d_c, K,
+                     d_ref, N, d_out, tiles);
+  return check_launch("fedagg_wsum_diff_f32");
 }
 
 int fedagg_dist2_f32(const float* const* d_src, int32_t K, const float* d_ref, const int64_t* d_chunks,

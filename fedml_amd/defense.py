@@ -66,6 +66,20 @@ that are pure reductions over the client axis.
                 of NEARMEDIAN_WIDE_AUTO, the same rule in torch ops above
                 that).  K >= 4f + 3.
 
+"fltrust"       Not in FedML: FLTrust (Cao, Fang, Liu, Gong, NDSS 2021) under
+                our own specification (fltrust, fltrust_coeffs), the one rule
+                here that assumes no honest majority and the one that judges
+                direction, not distance.  The server trains a root model of
+                its own from the global model on clean data; each client's
+                update is weighted by the ReLU of its cosine with the root
+                update and rescaled to the root update's norm.  Two passes
+                over the rows: every client's inner product with the root
+                update and its squared norm over the weight keys
+                (fedagg_dotnorm2_f32: exact products, fp64 sums, one read),
+                then global + sum c_i (x_i - global) over EVERY key for the
+                trusted clients only (fedagg_wsum_diff_f32); 2(K + 1) doubles
+                on the host in between.  Any number of clients.
+
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
                 the K x K squared distances of the clients' weight vectors are
@@ -134,9 +148,10 @@ DEFENSE_WEAK_DP = "weak_dp"
 DEFENSE_WISE_TRIMMED_MEAN = "wise_trimmed_mean"  # not a FedML defense type: Yin et al.'s per-coordinate rule
 DEFENSE_GEOMED = "geomed"  # not a FedML defense type either: our geometric median (RFA), see geometric_median
 DEFENSE_WISE_BULYAN = "wise_bulyan"  # not FedML's "bulyan": our specification of Bulyan, see bulyan
+DEFENSE_FLTRUST = "fltrust"  # not a FedML defense type: FLTrust (Cao et al.), see fltrust
 SUPPORTED = (DEFENSE_WISE_MEDIAN, DEFENSE_TRIMMED_MEAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_NORM_DIFF_CLIPPING,
              DEFENSE_SLSGD, DEFENSE_CCLIP, DEFENSE_ROBUST_LEARNING_RATE, DEFENSE_WEAK_DP, DEFENSE_WISE_TRIMMED_MEAN,
-             DEFENSE_GEOMED, DEFENSE_WISE_BULYAN)
+             DEFENSE_GEOMED, DEFENSE_WISE_BULYAN, DEFENSE_FLTRUST)
 # FedMLDefender constructs these but lists them under none of its
 # before / on / after-aggregation hooks (fedml_defender.py:131-154), so the
 # plugin path aggregates as if no defense were set; they act only through
@@ -1264,6 +1279,198 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
             kn.wsum_ptrs(torch.float32, table(alive), kn.weights_for(w32, torch.float32, dev), len(alive), g.length,
                          row, True)
         out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+    return (out, info) if return_info else out
+
+
+# ---- FLTrust (csrc/robust.hip: dotnorm2, wsum_diff) -----------------------------
+
+def dotnorm2_rows(d_ptrs: torch.Tensor, K: int, ref: torch.Tensor, direction: torch.Tensor, chunks: torch.Tensor,
+                  n_chunks: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dot, n2): for K fp32 device rows, the fp64 inner products of x_i - ref
+    with direction - ref and the fp64 squared norms of x_i - ref over the
+    chunked columns, in one read of the rows (fedagg_dotnorm2_f32).  Two views
+    of one 2K-double device tensor."""
+    kn._require_cuda(ref, "dotnorm2")
+    if ref.dtype != torch.float32 or direction.dtype != torch.float32:
+        raise TypeError("dotnorm2: fp32 rows")
+    out = torch.empty(2 * K, dtype=torch.float64, device=device)
+    work = _work(nat.WORK_DOTNORM2, K, n_chunks, device)
+    nat.check(nat.lib().fedagg_dotnorm2_f32(d_ptrs.data_ptr(), K, ref.data_ptr(), direction.data_ptr(),
+                                            chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(),
+                                            work.numel(), nat.stream_handle()), "dotnorm2")
+    return out[:K], out[K:]
+
+
+def wsum_diff_rows(d_ptrs: "torch.Tensor | None", d_c: "torch.Tensor | None", K: int, ref: torch.Tensor, N: int,
+                   out: torch.Tensor) -> None:
+    """out[:N] = ref + the chain of c_i (x_i - ref) over K fp32 device rows
+    (fedagg_wsum_diff_f32; K == 0: out = ref, no table needed).  d_c: K device
+    floats.  out aliases no input."""
+    kn._require_cuda(out, "wsum_diff")
+    if ref.dtype != torch.float32 or out.dtype != torch.float32:
+        raise TypeError("wsum_diff: fp32 rows and output")
+    nat.check(nat.lib().fedagg_wsum_diff_f32(d_ptrs.data_ptr() if K > 0 else None, d_c.data_ptr() if K > 0 else None,
+                                             K, ref.data_ptr(), N, out.data_ptr(), nat.stream_handle()), "wsum_diff")
+
+
+def dotnorm2_rows_torch(rows, ref, direction, cols=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The specification of fedagg_dotnorm2_f32 in torch ops, on any device.
+    rows: a (K, N) fp32 tensor or a list of K rows; cols: index tensor of the
+    columns that count (None: all).  Returns (dot, n2), K float64 each: the
+    fp64 sums of the exact products of the fp32 differences a_i = x_i - ref
+    with b = direction - ref, and of a_i with itself (torch's own summation
+    order: equal to the kernel's up to fp64 rounding, not bit for bit)."""
+    K = len(rows)
+    dev = ref.device
+    rc = ref if cols is None else ref[cols]
+    b = ((direction if cols is None else direction[cols]) - rc).double()
+    dot = torch.empty(K, dtype=torch.float64, device=dev)
+    n2 = torch.empty(K, dtype=torch.float64, device=dev)
+    for i in range(K):
+        a = ((rows[i] if cols is None else rows[i][cols]) - rc).double()
+        dot[i] = (a * b).sum()
+        n2[i] = (a * a).sum()
+    return dot, n2
+
+
+def wsum_diff_rows_torch(rows, c32, ref) -> torch.Tensor:
+    """The specification of fedagg_wsum_diff_f32 in torch ops, on any device:
+    acc = fl(c_0 fl(x_0 - ref)), acc = fl(acc + fl(c_i fl(x_i - ref))) client by
+    client, ref + acc at the end; ref itself (a copy) for no rows.  c32: K
+    coefficients (rounded to fp32 here).  Separate mul and add, each rounded
+    once, as the kernel's."""
+    K = len(rows)
+    if K == 0:
+        return ref.clone()
+    c = torch.tensor([float(v) for v in c32], dtype=torch.float64).to(torch.float32).to(ref.device)
+    acc = (rows[0] - ref) * c[0]
+    for i in range(1, K):
+        acc = acc + (rows[i] - ref) * c[i]
+    return ref + acc
+
+
+def fltrust_coeffs(dot, n2, nb2, lr: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
+    """FLTrust's trust scores and rebuild coefficients in float64, from the K
+    inner products dot_i = <a_i, b>, the K squared norms n2_i = |a_i|^2 and
+    nb2 = |b|^2 (a_i = client i's update, b the server's root update):
+
+        n_i = sqrt(n2_i), n_b = sqrt(nb2), cos_i = dot_i / (n_i n_b)
+        TS_i = cos_i if cos_i is finite and > 0 else 0        (ReLU)
+        S = sum TS_i, left to right
+        c_i = lr TS_i n_b / (n_i S)                            (0 where TS_i = 0)
+
+    so sum_i c_i a_i is the trust-weighted mean of the updates rescaled to the
+    root update's norm, times lr.  A client with a NaN, an inf, an overflowing
+    difference or a zero update has a non-finite or non-positive cosine and
+    gets trust 0.  S == 0: every c_i = 0 (the caller keeps the global model).
+    ValueError when n_b is 0 or not finite: a root update that does not move
+    cannot judge anything.  Returns (trust, coeffs), K float64 each."""
+    dot = np.asarray(dot, dtype=np.float64)
+    n2 = np.asarray(n2, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        nb = float(np.sqrt(np.float64(nb2)))
+        if not math.isfinite(nb) or nb == 0.0:
+            raise ValueError(f"fltrust: the root update's norm is {nb}: the server's root model must differ from the "
+                             f"global model by a finite amount")
+        n = np.sqrt(n2)
+        cos = dot / (n * nb)
+    trust = np.array([float(v) if math.isfinite(v) and v > 0 else 0.0 for v in cos], dtype=np.float64)
+    S = 0.0
+    for v in trust:
+        S += float(v)
+    coeffs = np.zeros(len(trust), dtype=np.float64)
+    if S > 0:
+        for i, ts in enumerate(trust):
+            if ts > 0:
+                coeffs[i] = float(lr) * ts * nb / (float(n[i]) * S)
+    return trust, coeffs
+
+
+class FLTrustInfo:
+    """What fltrust did: the float64 cosines `cos` (NaN for a non-finite or
+    zero update), the `trust` scores, the fp32 `coeffs` the rebuild used (as
+    float64 values, 0 for an untrusted client), the indices `trusted` and the
+    root update's norm `root_norm`."""
+
+    def __init__(self, cos, trust, coeffs, trusted, root_norm: float):
+        self.cos = cos
+        self.trust = trust
+        self.coeffs = coeffs
+        self.trusted = list(trusted)
+        self.root_norm = root_norm
+
+    def __repr__(self):
+        return f"FLTrustInfo(trusted={self.trusted}, root_norm={self.root_norm!r}, trust={self.trust})"
+
+
+def fltrust(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_model, root_model, lr: float = 1.0,
+            device=None, return_info: bool = False):
+    """FLTrust (Cao, Fang, Liu, Gong, NDSS 2021; the "fltrust" defense, ours:
+    FedML has none).  global_model: the server's current model g; root_model:
+    g after the server's own local training on its clean root data this round.
+    Client i's update a_i = x_i - g is weighted by the ReLU of its cosine with
+    the root update b = r - g and rescaled to |b|:
+
+        out = g + sum_i c_i (x_i - g),   (trust, c) = fltrust_coeffs(<a_i, b>, |a_i|^2, |b|^2, lr)
+
+    No honest majority is assumed; sample counts are ignored.  Cosines run
+    over the weight keys (is_weight_param, client 0's order) in one
+    fedagg_dotnorm2_f32 pass over the K client rows and the root row (row K:
+    its two sums are |b|^2), then one copy of 2(K + 1) doubles to the host.
+    The rebuild runs over EVERY key (BatchNorm statistics and counters too) in
+    one fedagg_wsum_diff_f32 pass over the trusted clients only, in ascending
+    order: an untrusted client's row is not in the pointer table, so its NaNs
+    are never read.  No trusted client (S == 0): a warning, and the result is g.
+
+    fp32 models (integer buffers allowed, entering as fl32(v) and coming back
+    fp32).  KeyError for a key of client 0 missing from another client, from
+    global_model or from root_model; ValueError when the root update is zero or
+    not finite.  Returns a new OrderedDict in client 0's key order on the
+    inputs' device; no input is modified.  return_info: also the FLTrustInfo."""
+    K = len(raw_client_grad_list)
+    if K < 1:
+        raise ValueError("fltrust: no clients")
+    dicts, keys = _client_dicts(raw_client_grad_list)
+    for k in keys:
+        global_model[k]
+        root_model[k]
+    if not keys:
+        info = FLTrustInfo(np.zeros(K), np.zeros(K), np.zeros(K), (), 0.0)
+        return (OrderedDict(), info) if return_info else OrderedDict()
+    _one_device(dicts[0], keys, "fltrust")
+    on_dev = dicts[0][keys[0]].is_cuda
+    bucket, dev = _float_bucket(dicts[0], K, "fltrust", device)
+    gb, _ = _float_bucket(dicts[0], 2, "fltrust", dev)  # the global and the root model, laid out like the clients
+    with torch.cuda.device(dev):
+        for i, d in enumerate(dicts):
+            _put_float(bucket, i, d, keys)
+        _put_float(gb, 0, global_model, keys)
+        _put_float(gb, 1, root_model, keys)
+        bucket.sync_ingest()
+        gb.sync_ingest()
+        g, gg = bucket.groups[torch.float32], gb.groups[torch.float32]
+        ref, root = gg.rows[0], gg.rows[1]
+        chunks, n_chunks = weight_chunks(g, nat.DIST_CHUNK, dev)
+        ptrs = kn.upload_i64([g.rows[i].data_ptr() for i in range(K)] + [root.data_ptr()], dev)
+        dot, n2 = dotnorm2_rows(ptrs, K + 1, ref, root, chunks, n_chunks, dev)
+        both = torch.cat([dot, n2]).cpu().numpy()  # 2(K + 1) doubles
+        dot, n2 = both[:K + 1], both[K + 1:]
+        trust, coeffs = fltrust_coeffs(dot[:K], n2[:K], n2[K], lr)
+        nb = float(np.sqrt(n2[K]))
+        with np.errstate(all="ignore"):
+            cos = dot[:K] / (np.sqrt(n2[:K]) * nb)
+        trusted = [i for i in range(K) if trust[i] > 0]
+        c32 = np.asarray(coeffs, dtype=np.float64).astype(np.float32)
+        if not trusted:
+            logging.warning("fltrust: no client's update has a positive cosine with the root update; "
+                            "the global model is kept")
+        row = torch.empty(g.padded, dtype=torch.float32, device=dev)
+        Kt = len(trusted)
+        t_ptrs = kn.upload_i64([g.rows[i].data_ptr() for i in trusted], dev) if Kt else None
+        d_c = kn.upload_f32([float(c32[i]) for i in trusted], dev) if Kt else None
+        wsum_diff_rows(t_ptrs, d_c, Kt, ref, g.length, row)
+        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+    info = FLTrustInfo(cos, trust, c32.astype(np.float64), trusted, nb)
     return (out, info) if return_info else out
 
 

@@ -14,7 +14,9 @@ aggregation), dispatched exactly as FedMLDefender does
 per-coordinate trimmed mean FedML lacks, and "geomed", our geometric median
 (RFA; FedML's own "geometric_median" / "RFA" stay refused), and "wise_bulyan",
 our Bulyan (repeated Krum, then per coordinate the mean of the values nearest
-the median; FedML's own "bulyan" stays refused) (all three on
+the median; FedML's own "bulyan" stays refused), and "fltrust", FLTrust (not in
+FedML: the server hands its root model over with set_fltrust_root before every
+round) (all four on
 aggregation); so do the distance-based
 "krum" / "multikrum", "norm_diff_clipping", "slsgd" and "cclip".  "robust_learning_rate" and
 "weak_dp" are accepted and, as in FedML, leave the plugin path a plain FedAvg
@@ -99,6 +101,7 @@ class ServerAggregator(ABC):
         self.final_contribution_assigment_dict = dict()
         self.eval_data = None
         self._cclip_guess = None  # CClip's initial guess, kept from before to after aggregation
+        self._fltrust_root = None  # FLTrust's root model for the coming round (set_fltrust_root)
 
     def is_main_process(self):
         return True
@@ -113,6 +116,13 @@ class ServerAggregator(ABC):
     @abstractmethod
     def set_model_params(self, model_parameters):
         pass
+
+    def set_fltrust_root(self, model_params) -> None:
+        """The server's root model for the coming round of the "fltrust"
+        defense: the state dict the server's own local training on its clean
+        root data gave, started from the current global model.  Not FedML's
+        interface (FLTrust is ours); one aggregate() uses it up."""
+        self._fltrust_root = model_params
 
     def on_before_aggregation(self, raw_client_model_or_grad_list: List[Tuple[float, OrderedDict]]):
         """server_aggregator.py:44-73 (FHE/DP/attacks disabled); the
@@ -161,6 +171,16 @@ class ServerAggregator(ABC):
             return dfn.bulyan(raw_client_model_or_grad_list, self.args.byzantine_client_num,
                               getattr(self.args, "fedagg_device", None),
                               getattr(self.args, "fedagg_pair_distance", "auto"))
+        if _defense(self.args) == dfn.DEFENSE_FLTRUST:
+            # not a FedML defense: FLTrust replaces the operator; the root model is used once, so a
+            # stale one cannot serve a second round silently
+            root = self._fltrust_root
+            if root is None:
+                raise RuntimeError("defense_type 'fltrust': no root model for this round; call set_fltrust_root("
+                                   "the server's own training result from the current global model) before aggregate")
+            self._fltrust_root = None
+            return dfn.fltrust(raw_client_model_or_grad_list, self.get_model_params(), root,
+                               getattr(self.args, "fltrust_lr", 1.0), getattr(self.args, "fedagg_device", None))
         if _defense(self.args) == dfn.DEFENSE_SLSGD:
             # defend_on_aggregation (slsgd_defense.py:54-67): the base operator, then the
             # moving average with the global model (extra_auxiliary_info, :81-85)

@@ -619,6 +619,60 @@ int fedagg_scale_diff_f32(const float* const* d_src, int32_t K, const float* d_r
                           const float* d_scale, int64_t N, float* const* d_dst,
                           fedagg_stream_t stream);
 
+/* The two passes of the FLTrust defense ("fltrust": Cao, Fang, Liu, Gong, NDSS
+ * 2021; not in FedML, specified at fedml_amd.defense.fltrust).  Both live in
+ * csrc/robust.hip.
+ *
+ * fedagg_dotnorm2_f32: every client's inner product with a direction and its
+ * squared norm, both about a reference row, in ONE read of the K rows.  Over
+ * the columns of the chunk table (the table fedagg_dist2_f32 takes: (start,
+ * length) int64 pairs, 1 <= length <= FEDAGG_DIST_CHUNK, start of any
+ * alignment; a column outside the table is not read), with
+ * a_i[e] = fl32(src_i[e] - d_ref[e]) and b[e] = fl32(d_dir[e] - d_ref[e]):
+ *   d_out[i]     = sum_e (double)a_i[e] * (double)b[e]      (i < K)
+ *   d_out[K + i] = sum_e (double)a_i[e]^2
+ * Each product of two fp32 values is exact in fp64; the sums are fp64, in the
+ * kernel's own but fixed order (per-block partials in d_work, combined
+ * without atomics): the exact sums up to fp64 rounding, and two calls on the
+ * same inputs give the same bits.  d_dir may itself be one of the rows: row j
+ * = d_dir gives d_out[j] and d_out[K + j] the same bits (the same products in
+ * the same order), which is how a caller gets |b|^2.  NaN and inf pass
+ * through into that client's two sums only.  d_work:
+ * fedagg_robust_work_len(FEDAGG_WORK_DOTNORM2, K, n_chunks) = 2 K
+ * min(n_chunks, 1024) doubles; a smaller one is accepted down to one chunk
+ * group's 2 K doubles and runs floor(work_len / 2K) chunk groups, as described
+ * above for dist2.  Any K >= 1.  n_chunks == 0: d_out = 0.  Stream-ordered;
+ * allocates nothing and does not synchronise.  FEDAGG_EINVAL (checked before
+ * any HIP call) for K < 1, n_chunks < 0, a null d_src, d_ref, d_dir or d_out,
+ * a null d_chunks or d_work with n_chunks > 0, or work_len < 2 K.
+ *
+ * fedagg_wsum_diff_f32: the reference row plus the weighted sum of the rows'
+ * differences to it, over the first N columns, as the fp32 chain
+ *   acc = fl32(d_c[0] * fl32(src_0[e] - d_ref[e]))
+ *   acc = fl32(acc + fl32(d_c[i] * fl32(src_i[e] - d_ref[e])))   i = 1 .. K - 1
+ *   d_out[e] = fl32(d_ref[e] + acc)
+ * the subtraction, the multiplication and each addition rounded separately,
+ * never an FMA.  K == 0: d_out[e] = d_ref[e] (d_src and d_c are not read and
+ * may be null).  d_c: K device floats.  One read of every row, one write of
+ * d_out; d_out aliases no input.  Rows, d_ref and d_out may have any 4-byte
+ * alignment: a pointer that is 16-byte aligned is accessed with 16-byte
+ * vectors, any other with 4-byte accesses, decided per pointer in the kernel
+ * (the row pointers are device memory), the same arithmetic either way.  A
+ * block works FEDAGG_WSUM_DIFF_TILE columns at a time; columns are indexed in
+ * 64 bits (N above 2^31 is fine).  Stream-ordered; allocates nothing and does
+ * not synchronise.  N == 0 is FEDAGG_OK without a launch.  FEDAGG_EINVAL
+ * (checked before any HIP call) for K < 0, N < 0, a null d_ref or d_out, or a
+ * null d_src or d_c with K > 0. */
+#define FEDAGG_WORK_DOTNORM2 5
+#define FEDAGG_WSUM_DIFF_TILE 2048
+int fedagg_dotnorm2_f32(const float* const* d_src, int32_t K, const float* d_ref,
+                        const float* d_dir, const int64_t* d_chunks,
+                        int64_t n_chunks, double* d_out /* 2K */, double* d_work,
+                        int64_t work_len, fedagg_stream_t stream);
+int fedagg_wsum_diff_f32(const float* const* d_src, const float* d_c, int32_t K,
+                         const float* d_ref, int64_t N, float* d_out,
+                         fedagg_stream_t stream);
+
 /* The robust-learning-rate defense (RobustLearningRateDefense.run,
  * core/security/defense/robust_learning_rate_defense.py:35-62, reached through
  * FedMLDefender.defend from simulation/mpi/fedavg/FedAVGAggregator.py:83-88):
