@@ -85,7 +85,11 @@ that are pure reductions over the client axis.
                 the K x K squared distances of the clients' weight vectors are
                 one pairdist2_rows call (fedagg_pairdist2_f32, or by default
                 the centred Gram on the matrix cores: fedagg_pairgram2_f32 up
-                to 128 clients, fedagg_pairgram2_wide_f32 from 129 to 1024);
+                to 128 clients, fedagg_pairgram2_wide_f32 from 129 to 1024).
+                An all-bf16 or all-f16 model stays 16-bit on the card:
+                fedagg_pairdist2_16, or fedagg_pairgram2_16 up to 128 clients
+                where PAIRGRAM16_AUTO measured it faster; a mixed-width float
+                model is widened exactly into fp32 rows;
                 the scores (sum of the K - f - 2 smallest; in numpy above 128
                 clients, bit for bit the reference's loop), their fp32 argsort
                 and the returned sub-list of the ORIGINAL (sample_num, dict)
@@ -120,7 +124,11 @@ norm does.  torch's own fp32 reduction may land one ulp away from that, so a
 Krum selection matches the reference's except between clients whose fp32
 scores are within an ulp (exact ties, e.g. mirror-image clients, can go either
 way in the reference too: its reduction order depends on the thread count),
-and a clipped client's divisor can differ in its last bit.
+and a clipped client's divisor can differ in its last bit.  16-bit rounds: Krum
+and multi-Krum take bf16 / f16 rows as they are (the differences of the exactly
+widened values, or the Gram about a centre rounded to the rows' dtype), like
+wise_median and wise_trimmed_mean; wise_bulyan, geomed, fltrust, cclip and
+norm_diff_clipping remain fp32-only.
 """
 from __future__ import annotations
 
@@ -580,6 +588,31 @@ def pairgram_wide_auto(K: int) -> bool:
     return _tier_auto(PAIRGRAM_WIDE_AUTO, PAIRGRAM_WIDE_MAX_CLIENTS, K)
 
 
+# Whether pairdist2_rows' "auto" runs the 16-bit Gram (fedagg_pairgram2_16) up
+# to 128 clients of that dtype, by PAIRGRAM_WIDE_AUTO's rule: True only if the
+# Gram's median time beat the 16-bit exact kernel's by more than the larger
+# min-max spread of the two at K = 128 and at the padded K = 100
+# (tools/pairgram16_probe.py -> profiles/pairgram16_probe.json, NOTES.md §5c,
+# DESIGN.md §5c).  Measured at 4,194,304 columns of base + small-update rows,
+# the paths launched alternately on the same rows, median of 10 (min - max),
+# exact / gram:
+#   bf16: K = 128  2.29 (2.28 - 2.40) / 0.60 (0.59 - 0.65) ms: gap 1.69 > 0.12;
+#         K = 100  1.68 (1.67 - 1.69) / 0.72 (0.71 - 0.73): gap 0.96 > 0.03
+#   f16:  K = 128  2.27 (2.25 - 2.29) / 0.65 (0.64 - 0.66): gap 1.62 > 0.04;
+#         K = 100  1.67 (1.66 - 1.68) / 0.81 (0.81 - 0.82): gap 0.86 > 0.02
+# (2.1x - 3.8x.)  The 16-bit exact kernel is built without packed fp32
+# operations (build.py, UNIT_FLAGS), so the same probe also times the fp32 exact
+# kernel, which has them, on the widened copy of the same rows: 1.96 (1.94 -
+# 2.03) ms at K = 128 and 1.55 (1.53 - 1.57) at K = 100, i.e. the 16-bit exact
+# kernel pays 1.17x / 1.09x for their absence, and the Gram wins against that
+# baseline too (gaps 1.37 / 0.83 ms for bf16, 1.31 / 0.74 for f16, spreads
+# <= 0.09): an entry is True only if it passes against both.  Against the fp32
+# Gram on the widened copy the 16-bit Gram is level, 0.94x - 1.07x: it saves the
+# fp32 copy, not time.
+PAIRGRAM16_AUTO = {torch.bfloat16: True, torch.float16: True}
+_PAIR16_DT = {torch.bfloat16: nat.DT_BF16, torch.float16: nat.DT_F16}
+
+
 def client_mean_row(d_ptrs: torch.Tensor, K: int, length: int, device, aligned: bool = False) -> torch.Tensor:
     """The mean of K fp32 device rows over their first `length` columns: one
     pass of the FedAvg kernel with device weights 1/K (the wide Gram's centre).
@@ -592,9 +625,11 @@ def client_mean_row(d_ptrs: torch.Tensor, K: int, length: int, device, aligned: 
 
 def pairdist2_rows(d_ptrs: torch.Tensor, K: int, chunks: torch.Tensor, n_chunks: int, device,
                    method: str = "auto", *, length: "int | None" = None,
-                   center: "torch.Tensor | None" = None, aligned: bool = False) -> torch.Tensor:
-    """K x K fp64 squared distances of K fp32 device rows over the chunked
-    columns.  method "exact": the reference's fp32 differences, squared and
+                   center: "torch.Tensor | None" = None, aligned: bool = False,
+                   dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """K x K fp64 squared distances of K device rows of `dtype` (fp32, bf16 or
+    f16) over the chunked columns.  fp32 rows, method "exact": the reference's
+    fp32 differences, squared and
     summed on the VALU (fedagg_pairdist2_f32); "gram": the centred Gram on the
     bf16 matrix cores with an exact three-way split (fedagg_pairgram2_f32,
     K <= 128); "gram_wide": the same Gram by 64-client tile pairs
@@ -608,9 +643,36 @@ def pairdist2_rows(d_ptrs: torch.Tensor, K: int, chunks: torch.Tensor, n_chunks:
     and the result is well conditioned (``gram_condition`` <=
     GRAM_MAX_CONDITION), else the exact kernel: one far-away update (the case
     Krum exists for) moves the client mean, and the honest clients' distances
-    would then carry the Gram's error scaled by that update's norm."""
+    would then carry the Gram's error scaled by that update's norm.
+
+    bf16 / f16 rows (csrc/robust16.hip): "exact" is fedagg_pairdist2_16 (the
+    same kernels on rows widened exactly as they load, any K); "gram" is
+    fedagg_pairgram2_16 (K <= 128: the centre rounded to the rows' dtype, one
+    to six MFMA products per stage as its values need); "gram_wide" is a
+    ValueError; "auto" runs the Gram up to 128 clients where PAIRGRAM16_AUTO
+    says so, with the same gram_condition fallback to the 16-bit exact kernel
+    (bit for bit its result), and the exact kernel elsewhere.  `length`,
+    `center` and `aligned` serve the wide Gram's centre pass only and are
+    ignored for 16-bit rows: the 16-bit Gram forms its centre per stage and
+    checks alignment in the kernel."""
     if method not in ("auto", "gram", "gram_wide", "exact"):
         raise ValueError(f"pair distance method {method!r}: 'auto', 'gram', 'gram_wide' or 'exact'")
+    if dtype != torch.float32 and dtype not in _PAIR16_DT:
+        raise TypeError(f"pair distances: fp32, bf16 or f16 rows (got {dtype})")
+    if dtype in _PAIR16_DT:
+        if method == "gram_wide":
+            raise ValueError("the wide Gram pair kernel takes fp32 rows only")
+        gram = method == "gram" or (method == "auto" and K <= GRAM_MAX_CLIENTS and PAIRGRAM16_AUTO[dtype])
+        if gram and K > GRAM_MAX_CLIENTS:
+            raise ValueError(f"the Gram pair kernel holds at most {GRAM_MAX_CLIENTS} clients (K = {K})")
+        out = torch.empty((K, K), dtype=torch.float64, device=device)
+        work = _work(nat.WORK_PAIRGRAM if gram else nat.WORK_PAIRDIST2, K, n_chunks, device)
+        fn = nat.lib().fedagg_pairgram2_16 if gram else nat.lib().fedagg_pairdist2_16
+        nat.check(fn(_PAIR16_DT[dtype], d_ptrs.data_ptr(), K, chunks.data_ptr(), n_chunks, out.data_ptr(),
+                     work.data_ptr(), work.numel(), nat.stream_handle()), "pairgram2_16" if gram else "pairdist2_16")
+        if gram and method == "auto" and gram_condition(out.cpu().numpy()) > GRAM_MAX_CONDITION:
+            return pairdist2_rows(d_ptrs, K, chunks, n_chunks, device, "exact", dtype=dtype)
+        return out
     gram = method == "gram" or (method == "auto" and K <= GRAM_MAX_CLIENTS)
     if gram and K > GRAM_MAX_CLIENTS:
         raise ValueError(f"the Gram pair kernel holds at most {GRAM_MAX_CLIENTS} clients (K = {K})")
@@ -657,9 +719,13 @@ def fp32_norm(sq: float) -> float:
     return float(np.float32(np.sqrt(sq)))
 
 
-def _weight_bucket(dicts: Sequence, what: str, device=None):
+def _weight_bucket(dicts: Sequence, what: str, device=None, dtypes=(torch.float32,)):
     """ClientBucket of the clients' weight keys (vectorize_weight's keys, in
-    client 0's order) and its fp32 row group."""
+    client 0's order) and its row group.  dtypes: the float dtypes the caller's
+    kernels take.  Weight keys all of one of them give rows of that dtype; keys
+    of several of them (a mixed-width float model) are declared fp32, so put()
+    widens the 16-bit keys exactly (median_row_dtype's rule); anything else,
+    integer weight keys included, is refused."""
     wkeys = [k for k in dicts[0].keys() if is_weight_param(k)]
     if not wkeys:
         raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")  # vectorize_weight on no keys
@@ -667,19 +733,23 @@ def _weight_bucket(dicts: Sequence, what: str, device=None):
         for k in wkeys:
             d[k]  # KeyError for a missing key, as the reference's walk would fail
     dts = {dicts[0][k].dtype for k in wkeys}
-    if dts != {torch.float32}:
-        raise NotImplementedError(f"{what} on the GPU takes fp32 weight keys (got {sorted(map(str, dts))})")
+    if not dts <= set(dtypes):
+        raise NotImplementedError(f"{what} on the GPU takes fp32 weight keys (got {sorted(map(str, dts))})"
+                                  if tuple(dtypes) == (torch.float32,) else
+                                  f"{what} on the GPU takes weight keys of {sorted(map(str, dtypes))} "
+                                  f"(got {sorted(map(str, dts))})")
+    row_dt = next(iter(dts)) if len(dts) == 1 else torch.float32
     _one_device(dicts[0], wkeys, what)
     t0 = dicts[0][wkeys[0]]
     dev = t0.device if t0.is_cuda else (torch.device(device) if device is not None else
                                         torch.device("cuda", torch.cuda.current_device()))
-    layout = [(k, tuple(dicts[0][k].shape), torch.float32) for k in wkeys]
+    layout = [(k, tuple(dicts[0][k].shape), row_dt) for k in wkeys]
     with torch.cuda.device(dev):
         bucket = ClientBucket(layout, len(dicts), dev)
         for i, d in enumerate(dicts):
             bucket.put(i, {k: d[k] for k in wkeys}, 1)
         bucket.sync_ingest()
-    return bucket, bucket.groups[torch.float32], wkeys, dev
+    return bucket, bucket.groups[row_dt], wkeys, dev
 
 
 def krum_scores(D: np.ndarray, byzantine_client_num: int) -> list:
@@ -741,11 +811,12 @@ def krum_before_aggregation(raw_client_grad_list: Sequence, byzantine_client_num
     if not 2 * byzantine_client_num + 2 <= num_client - krum_param_m:
         raise ValueError("byzantine_client_num conflicts with requirements in Krum: "
                          "2 * byzantine_client_num + 2 < client number - krum_param_m")
-    bucket, g, _, dev = _weight_bucket([item[1] for item in raw_client_grad_list], "krum", device)
+    bucket, g, _, dev = _weight_bucket([item[1] for item in raw_client_grad_list], "krum", device,
+                                       dtypes=(torch.float32, torch.bfloat16, torch.float16))
     with torch.cuda.device(dev):
         chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
         D = pairdist2_rows(g.d_ptrs, num_client, chunks, n_chunks, dev, method, length=g.length,
-                           aligned=True).cpu().numpy()
+                           aligned=True, dtype=g.dtype).cpu().numpy()
     scores = krum_scores(D, byzantine_client_num)
     score_index = torch.argsort(torch.Tensor(scores)).tolist()[0:krum_param_m]
     return [raw_client_grad_list[i] for i in score_index]

@@ -537,6 +537,52 @@ int fedagg_pairgram2_f32(const float* const* d_src, int32_t K,
                          const int64_t* d_chunks, int64_t n_chunks, double* d_out,
                          double* d_work, int64_t work_len, fedagg_stream_t stream);
 
+/* fedagg_pairdist2_f32 for K rows of dtype FEDAGG_DT_BF16 or FEDAGG_DT_F16
+ * (csrc/robust16.hip; any K).  Every element is widened to fp32 exactly when
+ * it is loaded; everything after the load is the fp32 kernel's source and
+ * arithmetic (the same fp32 subtracts and FMAs in the same order, issued
+ * unpacked in this unit: the same values, about the fp32 kernel's time):
+ *   d_out[i*K + j] = sum_e fl32(x_i[e] - x_j[e])^2,
+ * fp32 over a stage of <= 64 columns, fp64 across.  Chunk table (columns of
+ * the 16-bit rows, FEDAGG_PAIR_CHUNK, starts of any alignment), workspace
+ * (FEDAGG_WORK_PAIRDIST2), guarantees and errors as fedagg_pairdist2_f32;
+ * FEDAGG_EINVAL also for any other dtype. */
+int fedagg_pairdist2_16(int32_t dtype, const void* const* d_src, int32_t K,
+                        const int64_t* d_chunks, int64_t n_chunks, double* d_out,
+                        double* d_work, int64_t work_len, fedagg_stream_t stream);
+
+/* fedagg_pairgram2_f32 for K <= 128 rows of dtype FEDAGG_DT_BF16 or
+ * FEDAGG_DT_F16 (csrc/robust16.hip): the same chunk table (FEDAGG_PAIR_CHUNK,
+ * starts of any alignment; a stage takes 8-byte loads when the row pointers
+ * are 8-byte aligned and its first column is a multiple of 4, element loads
+ * otherwise), the same partials and finish.  Per 64-column stage
+ *   r = rne_dtype(fl32(column sum over the K clients * fl32(1 / K))),
+ *   c = fl32(x - r)   (x widened exactly),
+ * i.e. the centre is rounded to the rows' own dtype.  D is translation
+ * invariant, so this centre is as correct as the unrounded mean, and it makes
+ * c short: where r/2 <= x <= 2r (clients = a common base + small updates) c is
+ * exactly a value of the rows' dtype, a bf16 for bf16 rows (m = l = 0 in the
+ * split c = h + m + l) and at most 11 bits for f16 rows (l = 0).  The kernel
+ * finds the planes a stage needs while it splits and multiplies only those:
+ * hh alone, or hh, hm, mh, mm (all products exact), or the six products of
+ * fedagg_pairgram2_f32 with its three dropped terms.  A stage with a
+ * non-finite c runs all six.  fp32 over 4 stages, fp64 across, as there.
+ *   d_out[i*K + j] = max(0, G_ii + G_jj - (G_ij + G_ji)),
+ *   |error| ~ 1e-7 (|c_i|^2 + |c_j|^2), the norms taken about this centre.
+ * Guarantees as fedagg_pairgram2_f32: d_out is exactly symmetric, 0 on the
+ * diagonal, never negative, NaN / inf pass through (that client's row and
+ * column are non-finite).  Deterministic: per-block partials in d_work,
+ * combined in a fixed order.  d_work: fedagg_robust_work_len(
+ * FEDAGG_WORK_PAIRGRAM, K, n_chunks) doubles; a smaller one is accepted down
+ * to one chunk group's partials plus the K x K matrix, as described above.
+ * n_chunks == 0: d_out = 0.  Stream-ordered; allocates nothing and does not
+ * synchronise.  FEDAGG_EINVAL (checked before any HIP call) for a dtype other
+ * than the two, K < 1, K > 128, n_chunks < 0, a null d_src or d_out, a null
+ * d_chunks or d_work with n_chunks > 0, or a workspace below that minimum. */
+int fedagg_pairgram2_16(int32_t dtype, const void* const* d_src, int32_t K,
+                        const int64_t* d_chunks, int64_t n_chunks, double* d_out,
+                        double* d_work, int64_t work_len, fedagg_stream_t stream);
+
 /* The same K x K matrix for 1 <= K <= FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS, by
  * the same split Gram (c = h + m + l, the six bf16 MFMA products, fp32 over 4
  * stages, fp64 across) in a form whose blocks hold one pair of 64-client
