@@ -26,6 +26,18 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBS = 256;
 
+// A 16-byte load of four fp32 columns (any 4-byte alignment), non-temporal or plain.
+// NT = false for a row every wave of the block reads (the reference row):
+// a plain load leaves it in L2 for the other three waves; non-temporal loads
+// made each wave fetch it from HBM again (dist2's traffic was 1.05x the
+// algorithmic bytes, ~7 extra reference rows per call at config 3)
+template <bool NT = true>
+__device__ __forceinline__ f32x4 ld4(const float* p) {
+  const auto q = reinterpret_cast<const f32x4 __attribute__((address_space(1)))*>(gptr(p));
+  if constexpr (NT) return __builtin_nontemporal_load(q);
+  return *q;
+}
+
 // Row element types.  A 16-bit row is read as raw 16-bit words and widened to
 // fp32 exactly in registers: bf16 by a shift, f16 by v_cvt_f32_f16 (denormals
 // kept).  Everything after the load works on fp32 values, whatever the rows are.
@@ -600,6 +612,19 @@ __device__ __forceinline__ f32x4v split_mfma(const bf16x8v (&A)[3], const bf16x8
     x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[1], x, 0, 0, 0);
   }
   return x;
+}
+
+// c = h + m + l, four columns of one row, into the three planes at d
+[[maybe_unused]] __device__ __forceinline__ void split3_store(f32x4 cc, unsigned char* d, int plane) {
+  const uint32_t h01 = pk_bf16(cc.x, cc.y), h23 = pk_bf16(cc.z, cc.w);
+  const float e0 = cc.x - bf16_lo(h01), e1 = cc.y - bf16_hi(h01);
+  const float e2 = cc.z - bf16_lo(h23), e3 = cc.w - bf16_hi(h23);
+  const uint32_t m01 = pk_bf16(e0, e1), m23 = pk_bf16(e2, e3);
+  const uint32_t l01 = pk_bf16(e0 - bf16_lo(m01), e1 - bf16_hi(m01));
+  const uint32_t l23 = pk_bf16(e2 - bf16_lo(m23), e3 - bf16_hi(m23));
+  *reinterpret_cast<u32x2v*>(d) = u32x2v{h01, h23};
+  *reinterpret_cast<u32x2v*>(d + plane) = u32x2v{m01, m23};
+  *reinterpret_cast<u32x2v*>(d + 2 * plane) = u32x2v{l01, l23};
 }
 
 // pairgram_split8_kernel: the split Gram with 8 waves per block and ONE

@@ -40,6 +40,7 @@
 #include "pairdist.h"
 
 extern "C" int64_t fedagg_wsum_dist2_work_len_internal(int32_t K, int64_t n_chunks);
+extern "C" int64_t fedagg_histgram_work_len_internal(int32_t K, int64_t n_chunks);
 
 namespace {
 
@@ -61,17 +62,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 // `p`: 16-byte loads where a whole f32x4 lies in the chunk and p is 16-byte
 // aligned (bucket rows and key offsets are), 4-byte loads otherwise; columns
 // past len read 0.
-// NT = false for a row every wave of the block reads (the reference row):
-// a plain load leaves it in L2 for the other three waves; non-temporal loads
-// made each wave fetch it from HBM again (dist2's traffic was 1.05x the
-// algorithmic bytes, ~7 extra reference rows per call at config 3)
-template <bool NT = true>
-__device__ __forceinline__ f32x4 ld4(const float* p) {
-  const auto q = reinterpret_cast<const f32x4 __attribute__((address_space(1)))*>(gptr(p));
-  if constexpr (NT) return __builtin_nontemporal_load(q);
-  return *q;
-}
-
 template <bool NT = true>
 __device__ __forceinline__ void load_chunk(const float* p, int len, int lane, f32x4 (&v)[kLaneCols / 4]) {
   const bool al = (reinterpret_cast<uintptr_t>(p) & 15) == 0;
@@ -564,19 +554,6 @@ constexpr int kWideBlocks = 2048;               // blocks the grid aims for (one
 __constant__ constexpr int kWideDiag[8][3] = {{0, 0, 2}, {1, 1, 2}, {2, 2, 2}, {1, 3, 1},
                                               {0, 2, 1}, {0, 3, 1}, {0, 0, 0}, {3, 3, 1}};
 
-// c = h + m + l, four columns of one row, into the three planes at d
-__device__ __forceinline__ void split3_store(f32x4 cc, unsigned char* d, int plane) {
-  const uint32_t h01 = pk_bf16(cc.x, cc.y), h23 = pk_bf16(cc.z, cc.w);
-  const float e0 = cc.x - bf16_lo(h01), e1 = cc.y - bf16_hi(h01);
-  const float e2 = cc.z - bf16_lo(h23), e3 = cc.w - bf16_hi(h23);
-  const uint32_t m01 = pk_bf16(e0, e1), m23 = pk_bf16(e2, e3);
-  const uint32_t l01 = pk_bf16(e0 - bf16_lo(m01), e1 - bf16_hi(m01));
-  const uint32_t l23 = pk_bf16(e2 - bf16_lo(m23), e3 - bf16_hi(m23));
-  *reinterpret_cast<u32x2v*>(d) = u32x2v{h01, h23};
-  *reinterpret_cast<u32x2v*>(d + plane) = u32x2v{m01, m23};
-  *reinterpret_cast<u32x2v*>(d + 2 * plane) = u32x2v{l01, l23};
-}
-
 __global__ __launch_bounds__(kWideBS, 1) void pairgram_wide_kernel(const float* const* __restrict__ src, int K,
                                                                    const float* __restrict__ center,
                                                                    const int64_t* __restrict__ chunks,
@@ -969,6 +946,7 @@ int64_t fedagg_robust_work_len(int32_t kind, int32_t K, int64_t n_chunks) {
   }
   if (kind == FEDAGG_WORK_WSUM_DIST2) return fedagg_wsum_dist2_work_len_internal(K, n_chunks);  // geomed.hip
   if (kind == FEDAGG_WORK_DOTNORM2) return int64_t(2) * K * grid_groups(4, n_chunks, 0, 0);  // dist2's grid, two rows a client
+  if (kind == FEDAGG_WORK_HISTGRAM) return fedagg_histgram_work_len_internal(K, n_chunks);  // histgram.hip
   return -1;
 }
 

@@ -80,6 +80,23 @@ that are pure reductions over the client axis.
                 trusted clients only (fedagg_wsum_diff_f32); 2(K + 1) doubles
                 on the host in between.  Any number of clients.
 
+"foolsgold_cos" Not FedML's "foolsgold" (which stays refused: its source is not
+                mirrored here): FoolsGold (Fung, Yoon, Beschastnikh) under our
+                own name and specification (foolsgold, foolsgold_weights), the
+                one rule here with memory: it defends against sybils, clients
+                that each look plausible but push the same way round after
+                round.  The server keeps every client's accumulated update
+                (FoolsGoldState); a round adds x_i - global to the histories
+                and takes the cosine of every pair of them over the weight
+                keys.  Up to 128 clients that is ONE pass (fedagg_histgram_f32:
+                the history update in place and the uncentred split-bf16 Gram
+                on the matrix cores from the same registers); above 128, or
+                where HISTGRAM_AUTO says so, the history update in torch ops,
+                pairdist2_rows about a zero centre and dist2_rows.  K^2
+                doubles on the host give each client's weight alpha_i, then
+                global + sum c_i (x_i - global) over EVERY key for the clients
+                with alpha_i > 0 (fedagg_wsum_diff_f32).
+
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
                 the K x K squared distances of the clients' weight vectors are
@@ -127,8 +144,8 @@ way in the reference too: its reduction order depends on the thread count),
 and a clipped client's divisor can differ in its last bit.  16-bit rounds: Krum
 and multi-Krum take bf16 / f16 rows as they are (the differences of the exactly
 widened values, or the Gram about a centre rounded to the rows' dtype), like
-wise_median and wise_trimmed_mean; wise_bulyan, geomed, fltrust, cclip and
-norm_diff_clipping remain fp32-only.
+wise_median and wise_trimmed_mean; wise_bulyan, geomed, fltrust, foolsgold_cos,
+cclip and norm_diff_clipping remain fp32-only.
 """
 from __future__ import annotations
 
@@ -157,9 +174,10 @@ DEFENSE_WISE_TRIMMED_MEAN = "wise_trimmed_mean"  # not a FedML defense type: Yin
 DEFENSE_GEOMED = "geomed"  # not a FedML defense type either: our geometric median (RFA), see geometric_median
 DEFENSE_WISE_BULYAN = "wise_bulyan"  # not FedML's "bulyan": our specification of Bulyan, see bulyan
 DEFENSE_FLTRUST = "fltrust"  # not a FedML defense type: FLTrust (Cao et al.), see fltrust
+DEFENSE_FOOLSGOLD_COS = "foolsgold_cos"  # not FedML's "foolsgold" (refused): our specification, see foolsgold
 SUPPORTED = (DEFENSE_WISE_MEDIAN, DEFENSE_TRIMMED_MEAN, DEFENSE_KRUM, DEFENSE_MULTIKRUM, DEFENSE_NORM_DIFF_CLIPPING,
              DEFENSE_SLSGD, DEFENSE_CCLIP, DEFENSE_ROBUST_LEARNING_RATE, DEFENSE_WEAK_DP, DEFENSE_WISE_TRIMMED_MEAN,
-             DEFENSE_GEOMED, DEFENSE_WISE_BULYAN, DEFENSE_FLTRUST)
+             DEFENSE_GEOMED, DEFENSE_WISE_BULYAN, DEFENSE_FLTRUST, DEFENSE_FOOLSGOLD_COS)
 # FedMLDefender constructs these but lists them under none of its
 # before / on / after-aggregation hooks (fedml_defender.py:131-154), so the
 # plugin path aggregates as if no defense were set; they act only through
@@ -1542,6 +1560,316 @@ def fltrust(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mode
         wsum_diff_rows(t_ptrs, d_c, Kt, ref, g.length, row)
         out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
     info = FLTrustInfo(cos, trust, c32.astype(np.float64), trusted, nb)
+    return (out, info) if return_info else out
+
+
+# ---- FoolsGold (csrc/histgram.hip) ----------------------------------------------
+
+HISTGRAM_MAX_CLIENTS = GRAM_MAX_CLIENTS  # fedagg_histgram_f32 holds up to 128 clients
+# Whether foolsgold's "auto" runs the fused kernel up to 128 clients, by
+# PAIRGRAM_WIDE_AUTO's rule: True only if the composed path's median time
+# exceeds the fused kernel's by more than the larger min-max spread of the two
+# at K = 128 and at the padded K = 100 (tools/foolsgold_probe.py ->
+# profiles/foolsgold_probe.json, NOTES.md §5c).  Measured at
+# 4,194,304 fp32 columns, the two launched alternately on the same rows and
+# histories (restored before every launch), median of 10 (min - max),
+# composed / fused:
+#   K = 128  3.43 (3.42 - 3.75) / 1.19 (1.18 - 1.20) ms: gap 2.24 > 0.33;
+#   K = 100  3.01 (2.98 - 3.42) / 0.99 (0.98 - 1.01): gap 2.02 > 0.44
+# (2.9x - 3.0x; the fused pass moves its 3 K N 4 bytes at 5.4 / 5.1 TB/s.)
+HISTGRAM_AUTO = {128: True}
+
+
+def histgram_auto(K: int) -> bool:
+    """Whether foolsgold's "auto" runs fedagg_histgram_f32 for K clients."""
+    return _tier_auto(HISTGRAM_AUTO, HISTGRAM_MAX_CLIENTS, K)
+
+
+def histgram_rows(d_ptrs: torch.Tensor, K: int, ref: torch.Tensor, hist_ptrs: "torch.Tensor | None",
+                  chunks: torch.Tensor, n_chunks: int, device) -> torch.Tensor:
+    """The K x K fp64 Gram of a_i = fl(fl(x_i - ref) + h_i) over the chunked
+    columns of K <= 128 fp32 device rows, with a_i stored back into the history
+    rows (fedagg_histgram_f32, one pass).  hist_ptrs: the device table of the K
+    history rows' pointers, or None for a_i = fl(x_i - ref) and no store."""
+    kn._require_cuda(ref, "histgram")
+    if ref.dtype != torch.float32:
+        raise TypeError("histgram: fp32 rows")
+    if K > HISTGRAM_MAX_CLIENTS:
+        raise ValueError(f"the fused history-Gram kernel holds at most {HISTGRAM_MAX_CLIENTS} clients (K = {K})")
+    out = torch.empty((K, K), dtype=torch.float64, device=device)
+    work = _work(nat.WORK_HISTGRAM, K, n_chunks, device)
+    nat.check(nat.lib().fedagg_histgram_f32(d_ptrs.data_ptr(), K, ref.data_ptr(),
+                                            hist_ptrs.data_ptr() if hist_ptrs is not None else None,
+                                            chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(),
+                                            work.numel(), nat.stream_handle()), "histgram")
+    return out
+
+
+def histgram_rows_torch(rows, ref, hist=None, cols=None) -> torch.Tensor:
+    """The specification of fedagg_histgram_f32 in torch ops, on any device.
+    rows: a (K, N) fp32 tensor or a list of K rows; hist: the same of history
+    rows, updated IN PLACE on the columns that count, or None; cols: index
+    tensor of those columns (None: all).  a_i = (x_i - ref) + h_i, two fp32
+    roundings; returns the K x K float64 Gram of the a_i: exact products (two
+    fp32 values multiply exactly in fp64), fp64 sums in torch's order."""
+    K = len(rows)
+    rc = ref if cols is None else ref[cols]
+    A = torch.stack([(rows[i] if cols is None else rows[i][cols]) - rc for i in range(K)])
+    if hist is not None:
+        for i in range(K):
+            A[i] = A[i] + (hist[i] if cols is None else hist[i][cols])
+            if cols is None:
+                hist[i].copy_(A[i])
+            else:
+                hist[i][cols] = A[i]
+    Ad = A.double()
+    return Ad @ Ad.T
+
+
+def weight_segments(group) -> list:
+    """(offset, length) runs of a row group's weight-key columns, adjacent keys
+    merged: the columns weight_chunks cuts into pieces."""
+    segs = []
+    for key, off, n in zip(group.keys, group.offsets, group.numels):
+        if n == 0 or not is_weight_param(key):
+            continue
+        if segs and segs[-1][0] + segs[-1][1] == off:
+            segs[-1][1] += n
+        else:
+            segs.append([off, n])
+    return [(o, n) for o, n in segs]
+
+
+def histgram_rows_composed(x_rows: torch.Tensor, ref: torch.Tensor, hist: torch.Tensor, sel, hist_ptrs: torch.Tensor,
+                           K: int, segs, chunks: torch.Tensor, n_chunks: int, device,
+                           zero: "torch.Tensor | None" = None) -> torch.Tensor:
+    """histgram_rows' result from the kernels that were there before it, for
+    any K: the history update in torch ops (histgram_rows_torch's, bit for
+    bit), then G_ij = (n_i + n_j - D_ij) / 2 from the histories' squared
+    distances (pairdist2_rows, "auto" about a zero centre) and squared norms
+    n_i (dist2_rows), G_ii = n_i.  x_rows: (K, P) fp32; hist: the state's (R, P)
+    row tensor; sel: the K history rows' indices in it (None: the first K);
+    hist_ptrs: their pointer table; segs: weight_segments; zero: a zero fp32
+    row of P columns (made here when None)."""
+    for off, n in segs:
+        upd = x_rows[:K, off:off + n] - ref[off:off + n]
+        if sel is None:
+            hist[:K, off:off + n] += upd  # fl(h + u) = fl(u + h)
+        else:
+            hist[sel, off:off + n] = upd + hist[sel, off:off + n]
+    if zero is None:
+        zero = torch.zeros(hist.shape[1], dtype=torch.float32, device=device)
+    D = pairdist2_rows(hist_ptrs, K, chunks, n_chunks, device, "auto", center=zero, length=hist.shape[1])
+    n2 = dist2_rows(hist_ptrs, K, None, chunks, n_chunks, device)
+    G = (n2[:, None] + n2[None, :] - D) * 0.5
+    G.diagonal().copy_(n2)
+    return G
+
+
+def foolsgold_weights(G, confidence: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
+    """FoolsGold's per-client weights in float64 from the K x K Gram G of the
+    clients' accumulated updates (G_ii = |a_i|^2).  A client takes part when
+    G_ii is finite and its row of G is finite against every client with a
+    finite G_jj; the others get alpha = 0 and enter nobody's maxima.  Among the
+    clients taking part (every max over j != i; an empty max is 0):
+
+        cs_ij = G_ij / sqrt(G_ii G_jj)       (0 when G_ii or G_jj is 0: an empty history)
+        v_i = max_j cs_ij
+        cs'_ij = cs_ij v_i / v_j  where v_j > v_i and v_j > 0, else cs_ij    (pardoning)
+        w_i = clip(1 - max_j cs'_ij, 0, 1);  w = w / max w;  w == 1 becomes 0.99
+        alpha_i = clip(confidence (ln(w_i / (1 - w_i)) + 0.5), 0, 1)
+
+    max w == 0 (every client is somebody's copy): every alpha = 0.  K == 1:
+    alpha = [1].  sqrt(fl(g g)) == g in IEEE arithmetic, so two clients with
+    identical histories (G_ij == G_ii == G_jj) have cs_ij == 1 exactly.
+    Returns (alpha, cs): K weights and the K x K cosines before pardoning (0 on
+    the diagonal and for clients not taking part)."""
+    G = np.array(G, dtype=np.float64)
+    K = G.shape[0]
+    d = np.diag(G).copy()
+    part = np.isfinite(d)
+    part &= np.isfinite(G[:, part]).all(axis=1)
+    alpha = np.zeros(K, dtype=np.float64)
+    cs = np.zeros((K, K), dtype=np.float64)
+    idx = np.flatnonzero(part)
+    if idx.size == 0:
+        return alpha, cs
+    Gp, dp = G[np.ix_(idx, idx)], d[idx]
+    pos = dp > 0
+    with np.errstate(all="ignore"):
+        den = np.sqrt(dp[:, None] * dp[None, :])
+        c = np.where(pos[:, None] & pos[None, :], Gp / np.where(den > 0, den, 1.0), 0.0)
+    np.fill_diagonal(c, 0.0)
+    cs[np.ix_(idx, idx)] = c
+    off = ~np.eye(idx.size, dtype=bool)
+
+    def rowmax(m):
+        return np.where(off, m, -np.inf).max(axis=1) if idx.size > 1 else np.zeros(idx.size)
+
+    v = rowmax(c)
+    pard = (v[None, :] > v[:, None]) & (v[None, :] > 0)
+    with np.errstate(all="ignore"):
+        cp = np.where(pard, c * v[:, None] / np.where(pard, v[None, :], 1.0), c)
+    w = np.clip(1.0 - rowmax(cp), 0.0, 1.0)
+    mw = float(w.max())
+    if mw == 0.0:
+        return alpha, cs
+    w = w / mw
+    w[w == 1.0] = 0.99
+    with np.errstate(all="ignore"):
+        a = float(confidence) * (np.log(w / (1.0 - w)) + 0.5)
+    alpha[idx] = np.clip(np.where(np.isnan(a), 0.0, a), 0.0, 1.0)
+    return alpha, cs
+
+
+class FoolsGoldState:
+    """The server's memory for "foolsgold_cos": one fp32 device row per client
+    ever seen, the sum of its updates so far, laid out like the clients' fp32
+    bucket rows (the group's padded columns; only the weight keys' columns are
+    ever written), zero-filled.  Created empty; the first round binds it to
+    that round's layout and device, and a later round with another layout or
+    device raises ValueError.  Capacity grows by doubling."""
+
+    def __init__(self):
+        self.rows: "torch.Tensor | None" = None
+        self.slots: dict = {}
+        self.layout = None
+        self.device = None
+
+    def bind(self, group, device) -> None:
+        layout = (tuple(group.keys), tuple(group.offsets), tuple(group.numels), int(group.rows.shape[1]))
+        if self.layout is None:
+            self.layout, self.device = layout, torch.device(device)
+        elif layout != self.layout or torch.device(device) != self.device:
+            raise ValueError("foolsgold: this round's model layout or device differs from the one the state's "
+                             "histories were accumulated on; start a new FoolsGoldState")
+
+    def rows_for(self, client_ids) -> list:
+        """The history row index of each id (new ids get fresh zero rows)."""
+        for cid in client_ids:
+            if cid not in self.slots:
+                self.slots[cid] = len(self.slots)
+        need = len(self.slots)
+        have = 0 if self.rows is None else self.rows.shape[0]
+        if need > have:
+            cap = max(need, 2 * have, 8)
+            new = torch.zeros((cap, self.layout[3]), dtype=torch.float32, device=self.device)
+            if have:
+                new[:have].copy_(self.rows)
+            self.rows = new
+        return [self.slots[cid] for cid in client_ids]
+
+    def reset(self, client_id) -> None:
+        """Forget one client's history (its row becomes zero again)."""
+        if client_id in self.slots and self.rows is not None:
+            self.rows[self.slots[client_id]].zero_()
+
+
+class FoolsGoldInfo:
+    """What foolsgold did: the float64 weights `alpha`, the cosines `cs`
+    (foolsgold_weights), the fp32 `coeffs` the rebuild used (as float64 values,
+    0 for an excluded client) and the `method` that ran ("fused" or "composed")."""
+
+    def __init__(self, alpha, cs, coeffs, method: str):
+        self.alpha = alpha
+        self.cs = cs
+        self.coeffs = coeffs
+        self.method = method
+
+    def __repr__(self):
+        return f"FoolsGoldInfo(method={self.method!r}, alpha={self.alpha})"
+
+
+def foolsgold(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_model, state: FoolsGoldState,
+              client_ids=None, confidence: float = 1.0, device=None, method: str = "auto",
+              return_info: bool = False):
+    """FoolsGold (Fung, Yoon, Beschastnikh; the "foolsgold_cos" defense, ours:
+    FedML's "foolsgold" is not reproduced).  global_model: the server's current
+    model g; state: the FoolsGoldState kept across rounds; client_ids: who sent
+    each update (default range(K); hashable, no duplicates), the key of a
+    client's history.  A round
+
+      1. adds a_i = x_i - g to client i's history h_i over the weight keys
+         (is_weight_param; fl(fl(x_i - g) + h_i) in fp32) and takes the Gram of
+         the updated histories: method "fused", fedagg_histgram_f32 in one pass
+         (K <= 128, ValueError above); "composed", histgram_rows_composed (any
+         K); "auto", fused where HISTGRAM_AUTO says so, else composed;
+      2. (alpha, cs) = foolsgold_weights(G, confidence) on the host;
+      3. out = g + sum_i c_i (x_i - g) over EVERY key (BatchNorm statistics and
+         counters too) in one fedagg_wsum_diff_f32 pass over the clients with
+         alpha_i > 0, in ascending order (an excluded client's row is not in
+         the pointer table), c_i = fl32(alpha_i n_i / sum_j n_j) with the
+         sample counts n of all K clients: alpha = 1 is sample-weighted FedAvg
+         of the updates.  Every alpha = 0: a warning, and the result is g.
+
+    A client whose history came out non-finite (it sent a NaN or an inf) is
+    reset after the round.  fp32 models (integer buffers allowed, entering as
+    fl32(v) and coming back fp32).  KeyError for a key of client 0 missing from
+    another client or from global_model.  Returns a new OrderedDict in client
+    0's key order on the inputs' device; no input is modified.  return_info:
+    also the FoolsGoldInfo."""
+    K = len(raw_client_grad_list)
+    if K < 1:
+        raise ValueError("foolsgold: no clients")
+    if method not in ("auto", "fused", "composed"):
+        raise ValueError(f"foolsgold method {method!r}: 'auto', 'fused' or 'composed'")
+    ids = list(range(K)) if client_ids is None else list(client_ids)
+    if len(ids) != K:
+        raise ValueError(f"foolsgold: {len(ids)} client ids for {K} clients")
+    if len(set(ids)) != K:
+        raise ValueError("foolsgold: duplicate client ids in one round")
+    if method == "fused" and K > HISTGRAM_MAX_CLIENTS:
+        raise ValueError(f"foolsgold method 'fused' holds at most {HISTGRAM_MAX_CLIENTS} clients (K = {K}); "
+                         f"'composed' serves any K")
+    if not isinstance(state, FoolsGoldState):
+        raise TypeError("foolsgold: state must be a FoolsGoldState")
+    fused = method == "fused" or (method == "auto" and histgram_auto(K))
+    dicts, keys = _client_dicts(raw_client_grad_list)
+    for k in keys:
+        global_model[k]
+    if not keys:
+        info = FoolsGoldInfo(np.zeros(K), np.zeros((K, K)), np.zeros(K), "fused" if fused else "composed")
+        return (OrderedDict(), info) if return_info else OrderedDict()
+    _one_device(dicts[0], keys, "foolsgold")
+    on_dev = dicts[0][keys[0]].is_cuda
+    bucket, dev = _float_bucket(dicts[0], K, "foolsgold", device)
+    gb, _ = _float_bucket(dicts[0], 1, "foolsgold", dev)  # the global model, laid out like the clients
+    with torch.cuda.device(dev):
+        for i, d in enumerate(dicts):
+            _put_float(bucket, i, d, keys)
+        _put_float(gb, 0, global_model, keys)
+        bucket.sync_ingest()
+        gb.sync_ingest()
+        g, ref = bucket.groups[torch.float32], gb.groups[torch.float32].rows[0]
+        state.bind(g, dev)
+        sel = state.rows_for(ids)
+        chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
+        hist_ptrs = kn.upload_i64([state.rows[r].data_ptr() for r in sel], dev)
+        if fused:
+            G = histgram_rows(g.d_ptrs, K, ref, hist_ptrs, chunks, n_chunks, dev)
+        else:
+            first = sel == list(range(K))
+            G = histgram_rows_composed(g.rows, ref, state.rows, None if first else torch.tensor(sel, device=dev),
+                                       hist_ptrs, K, weight_segments(g), chunks, n_chunks, dev)
+        G = G.cpu().numpy()
+        alpha, cs = foolsgold_weights(G, confidence)
+        for i in range(K):
+            if not math.isfinite(G[i, i]):
+                state.reset(ids[i])
+        n = np.array([float(raw_client_grad_list[i][0]) for i in range(K)], dtype=np.float64)
+        c32 = (alpha * n / n.sum()).astype(np.float32)
+        incl = [i for i in range(K) if alpha[i] > 0]
+        if not incl:
+            logging.warning("foolsgold: every client's weight is 0 (each is another's copy, or non-finite); "
+                            "the global model is kept")
+        row = torch.empty(g.rows.shape[1], dtype=torch.float32, device=dev)
+        Ki = len(incl)
+        i_ptrs = kn.upload_i64([g.rows[i].data_ptr() for i in incl], dev) if Ki else None
+        d_c = kn.upload_f32([float(c32[i]) for i in incl], dev) if Ki else None
+        wsum_diff_rows(i_ptrs, d_c, Ki, ref, g.length, row)
+        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+    coeffs = np.where(alpha > 0, c32.astype(np.float64), 0.0)
+    info = FoolsGoldInfo(alpha, cs, coeffs, "fused" if fused else "composed")
     return (out, info) if return_info else out
 
 

@@ -16,7 +16,9 @@ per-coordinate trimmed mean FedML lacks, and "geomed", our geometric median
 our Bulyan (repeated Krum, then per coordinate the mean of the values nearest
 the median; FedML's own "bulyan" stays refused), and "fltrust", FLTrust (not in
 FedML: the server hands its root model over with set_fltrust_root before every
-round) (all four on
+round), and "foolsgold_cos", our FoolsGold (the aggregator keeps the clients'
+update histories across rounds; set_foolsgold_clients names each round's
+clients; FedML's own "foolsgold" stays refused) (all five on
 aggregation); so do the distance-based
 "krum" / "multikrum", "norm_diff_clipping", "slsgd" and "cclip".  "robust_learning_rate" and
 "weak_dp" are accepted and, as in FedML, leave the plugin path a plain FedAvg
@@ -102,6 +104,8 @@ class ServerAggregator(ABC):
         self.eval_data = None
         self._cclip_guess = None  # CClip's initial guess, kept from before to after aggregation
         self._fltrust_root = None  # FLTrust's root model for the coming round (set_fltrust_root)
+        self._foolsgold_state = dfn.FoolsGoldState()  # "foolsgold_cos": the clients' update histories
+        self._foolsgold_clients = None  # the coming round's client ids (set_foolsgold_clients)
 
     def is_main_process(self):
         return True
@@ -123,6 +127,13 @@ class ServerAggregator(ABC):
         root data gave, started from the current global model.  Not FedML's
         interface (FLTrust is ours); one aggregate() uses it up."""
         self._fltrust_root = model_params
+
+    def set_foolsgold_clients(self, client_ids) -> None:
+        """Who sends the coming round's updates, in the order of the list
+        aggregate() will get: the keys of the "foolsgold_cos" defense's
+        histories (without it the clients count as 0 .. K - 1 every round).
+        Not FedML's interface; one aggregate() uses it up."""
+        self._foolsgold_clients = list(client_ids)
 
     def on_before_aggregation(self, raw_client_model_or_grad_list: List[Tuple[float, OrderedDict]]):
         """server_aggregator.py:44-73 (FHE/DP/attacks disabled); the
@@ -181,6 +192,14 @@ class ServerAggregator(ABC):
             self._fltrust_root = None
             return dfn.fltrust(raw_client_model_or_grad_list, self.get_model_params(), root,
                                getattr(self.args, "fltrust_lr", 1.0), getattr(self.args, "fedagg_device", None))
+        if _defense(self.args) == dfn.DEFENSE_FOOLSGOLD_COS:
+            # not a FedML defense: FoolsGold replaces the operator; the ids are used once, so a
+            # stale list cannot name another round's clients
+            ids, self._foolsgold_clients = self._foolsgold_clients, None
+            return dfn.foolsgold(raw_client_model_or_grad_list, self.get_model_params(), self._foolsgold_state, ids,
+                                 getattr(self.args, "foolsgold_confidence", 1.0),
+                                 getattr(self.args, "fedagg_device", None),
+                                 getattr(self.args, "fedagg_foolsgold_method", "auto"))
         if _defense(self.args) == dfn.DEFENSE_SLSGD:
             # defend_on_aggregation (slsgd_defense.py:54-67): the base operator, then the
             # moving average with the global model (extra_auxiliary_info, :81-85)

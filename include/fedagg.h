@@ -719,6 +719,45 @@ int fedagg_wsum_diff_f32(const float* const* d_src, const float* d_c, int32_t K,
                          const float* d_ref, int64_t N, float* d_out,
                          fedagg_stream_t stream);
 
+/* The fused pass of the "foolsgold_cos" defense (FoolsGold: Fung, Yoon,
+ * Beschastnikh; ours, specified at fedml_amd.defense.foolsgold; FedML's own
+ * "foolsgold" is not reproduced).  csrc/histgram.hip.  For every column e of
+ * the chunk table (the table fedagg_pairgram2_f32 takes: (start, length) int64
+ * pairs, 1 <= length <= FEDAGG_PAIR_CHUNK, start of any alignment, every
+ * column in at most one chunk) and every client i < K, 1 <= K <= 128:
+ *   a_i[e] = fl32( fl32(src_i[e] - d_ref[e]) + d_hist[i][e] ),
+ *   d_hist[i][e] = a_i[e]                      (the history row, in place)
+ *   d_out[i*K + j] = sum_e a_i[e] a_j[e]       (fp64; the squared norms on the
+ *                                               diagonal)
+ * the subtraction and the addition rounded separately.  d_hist == NULL:
+ * a_i[e] = fl32(src_i[e] - d_ref[e]) and nothing is stored.  A column outside
+ * the table is neither read nor written.  The K history rows alias each other
+ * and every other argument nowhere.  The Gram is fedagg_pairgram2_f32's
+ * without its centre: each a split exactly into three bf16 parts h + m + l,
+ * six v_mfma_f32_16x16x32_bf16 products per 32 columns, fp32 over 4 stages of
+ * 64 columns, fp64 across: |d_out[i*K + j] - exact| ~ 1e-7 |a_i| |a_j|, i.e.
+ * an absolute ~1e-7 in the cosine.  d_out equals its transpose bit for bit
+ * (both triangles are written from one sum).  NaN and inf pass through into
+ * that client's history, row and column.  Deterministic: per-block partials in
+ * d_work, combined in a fixed order.  d_work: fedagg_robust_work_len(
+ * FEDAGG_WORK_HISTGRAM, K, n_chunks) = min(n_chunks, 256) * T(T + 1)/2 * 256
+ * doubles, T = ceil(K / 16) (-1 there for K > 128); a smaller one is accepted
+ * down to one chunk group's T(T + 1)/2 * 256 doubles and runs fewer chunk
+ * groups, as described above.  n_chunks == 0: d_out = 0, nothing else is
+ * touched.  Rows, d_ref and history rows may have any 4-byte alignment.
+ * Stream-ordered; allocates nothing and does not synchronise.  FEDAGG_EINVAL
+ * (checked before any HIP call) for K < 1, K > 128, n_chunks < 0, a null
+ * d_src, d_ref or d_out, a null d_chunks or d_work with n_chunks > 0, or a
+ * workspace below that minimum. */
+/* 6 and 7 stay unassigned: fedagg_robust_work_len keeps answering -1 for them, as
+ * callers of the earlier header could rely on */
+#define FEDAGG_WORK_HISTGRAM 8
+int fedagg_histgram_f32(const float* const* d_src, int32_t K, const float* d_ref,
+                        float* const* d_hist /* NULL: no history */,
+                        const int64_t* d_chunks, int64_t n_chunks,
+                        double* d_out /* K x K */, double* d_work, int64_t work_len,
+                        fedagg_stream_t stream);
+
 /* The robust-learning-rate defense (RobustLearningRateDefense.run,
  * core/security/defense/robust_learning_rate_defense.py:35-62, reached through
  * FedMLDefender.defend from simulation/mpi/fedavg/FedAVGAggregator.py:83-88):
