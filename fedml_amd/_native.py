@@ -103,6 +103,7 @@ SIGNATURES = {
     "fedagg_robust_work_len": (_I64, [_I32, _I32, _I64]),
     "fedagg_dist2_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_wsum_dist2_f32": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _U32, _P]),
+    "fedagg_wsum_dist2_16": (ctypes.c_int, [_I32, _P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _U32, _P]),
     "fedagg_pairdist2_f32": (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_pairgram2_f32": (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_pairdist2_16": (ctypes.c_int, [_I32, _P, _I32, _P, _I64, _P, _P, _I64, _P]),

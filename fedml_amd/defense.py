@@ -44,7 +44,14 @@ that are pure reductions over the client axis.
                 is one pass over the rows: the weighted sum z and every
                 client's distance to it (fedagg_wsum_dist2_f32, up to 128
                 clients; fedagg_wsum_f32 + fedagg_dist2_f32 above that and
-                where "auto" measured the pair faster).  FedML's own
+                where "auto" measured the pair faster).  An all-bf16 or
+                all-f16 model of device-resident clients is accepted (host
+                dicts of one stay refused): up to 128 clients its rows can stay
+                16-bit on the card (fedagg_wsum_dist2_16: widened exactly as
+                they load, an fp32 iterate, the result rounded once), which
+                "fused" always does and "auto" where GEOMED16_AUTO measured it
+                faster; elsewhere the clients are widened exactly into fp32
+                rows and the result is rounded once.  FedML's own
                 "geometric_median" / "RFA" loop (a Python set of weights, a
                 truncating zip) is NOT reproduced: those names stay refused.
 
@@ -144,13 +151,16 @@ way in the reference too: its reduction order depends on the thread count),
 and a clipped client's divisor can differ in its last bit.  16-bit rounds: Krum
 and multi-Krum take bf16 / f16 rows as they are (the differences of the exactly
 widened values, or the Gram about a centre rounded to the rows' dtype), like
-wise_median and wise_trimmed_mean; wise_bulyan, geomed, fltrust, foolsgold_cos,
-cclip and norm_diff_clipping remain fp32-only.
+wise_median and wise_trimmed_mean; geomed takes all-bf16 / all-f16 models of
+device-resident clients too (the fused pass on 16-bit rows, or an exact widening into fp32 rows; an fp32
+iterate and one final rounding either way); wise_bulyan, fltrust,
+foolsgold_cos, cclip and norm_diff_clipping remain fp32-only.
 """
 from __future__ import annotations
 
 import logging
 import math
+import types
 from collections import OrderedDict
 from typing import List, Sequence, Tuple
 
@@ -897,12 +907,15 @@ def _like_input(out: "OrderedDict[str, torch.Tensor]", on_device: bool) -> "Orde
     return OrderedDict((k, t.cpu()) for k, t in out.items())
 
 
-def _float_bucket(template, capacity: int, what: str, device=None):
+def _float_bucket(template, capacity: int, what: str, device=None, widen: "torch.dtype | None" = None):
     """A ClientBucket for fp32 models (integer buffers allowed: they sit in
     the fp32 row as fl32(v), the dtype torch's int64 * float yields), laid out
-    by `template`'s keys, on its device (or `device` for host tensors)."""
+    by `template`'s keys, on its device (or `device` for host tensors).
+    widen: keys of this 16-bit dtype are declared fp32, so put() widens them
+    exactly."""
     keys = list(template.keys())
-    layout = [(k, tuple(template[k].shape), template[k].dtype) for k in keys]
+    layout = [(k, tuple(template[k].shape), torch.float32 if template[k].dtype == widen else template[k].dtype)
+              for k in keys]
     dts = {dt for _, _, dt in layout}
     if not dts <= {torch.float32, torch.int64, torch.int32} or torch.float32 not in dts:
         raise NotImplementedError(f"{what} on the GPU takes fp32 models (integer buffers allowed), got "
@@ -1135,22 +1148,29 @@ class GeomedInfo:
 
 
 def wsum_dist2_rows(d_ptrs: torch.Tensor, d_w, K: int, chunks: torch.Tensor, n_chunks: int, z: torch.Tensor,
-                    device) -> torch.Tensor:
-    """One fused Weiszfeld pass (fedagg_wsum_dist2_f32): the weighted sum of
-    the K fp32 device rows into z's chunked columns and, returned, the K fp64
-    squared distances of the rows to it over those columns.  d_w: K device
-    floats or kernels.HostWeights.  K <= GEOMED_MAX_CLIENTS."""
+                    device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One fused Weiszfeld pass (fedagg_wsum_dist2_f32; fedagg_wsum_dist2_16
+    for bf16 / f16 rows, widened exactly as they load): the weighted sum of
+    the K device rows of `dtype` into the fp32 z's chunked columns and,
+    returned, the K fp64 squared distances of the rows to it over those
+    columns.  d_w: K device floats or kernels.HostWeights.
+    K <= GEOMED_MAX_CLIENTS."""
     kn._require_cuda(z, "wsum_dist2")
     if z.dtype != torch.float32:
         raise TypeError("wsum_dist2: fp32 rows and output")
+    if dtype != torch.float32 and dtype not in _PAIR16_DT:
+        raise TypeError(f"wsum_dist2: fp32, bf16 or f16 rows (got {dtype})")
     out = torch.empty(K, dtype=torch.float64, device=device)
     work = _work(nat.WORK_WSUM_DIST2, K, n_chunks, device)
     flags = nat.FEDAGG_ALIGNED16 if z.data_ptr() % 16 == 0 else 0  # the kernel has one form for every alignment
     if isinstance(d_w, kn.HostWeights):
         flags |= nat.FEDAGG_HOST_WEIGHTS
-    nat.check(nat.lib().fedagg_wsum_dist2_f32(d_ptrs.data_ptr(), d_w.data_ptr(), K, chunks.data_ptr(), n_chunks,
-                                              z.data_ptr(), out.data_ptr(), work.data_ptr(), work.numel(), flags,
-                                              nat.stream_handle()), "wsum_dist2")
+    a = (d_ptrs.data_ptr(), d_w.data_ptr(), K, chunks.data_ptr(), n_chunks, z.data_ptr(), out.data_ptr(),
+         work.data_ptr(), work.numel(), flags, nat.stream_handle())
+    if dtype == torch.float32:
+        nat.check(nat.lib().fedagg_wsum_dist2_f32(*a), "wsum_dist2")
+    else:
+        nat.check(nat.lib().fedagg_wsum_dist2_16(_PAIR16_DT[dtype], *a), "wsum_dist2_16")
     return out
 
 
@@ -1297,6 +1317,17 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
     measured faster (GEOMED_AUTO_FUSED) and the pair elsewhere and above 128
     clients.  One K-double device-to-host copy per pass, as Krum's.
 
+    All-bf16 and all-f16 models (integer buffers allowed) are taken too when
+    the clients' tensors are on the device; host dicts of a 16-bit model stay
+    refused (NotImplementedError), like mixed-width float models.  Up
+    to 128 clients, for "fused" and where "auto" finds GEOMED16_AUTO True, the
+    rows stay 16-bit on the card and every pass is one fedagg_wsum_dist2_16
+    launch (_geometric_median16); otherwise ("unfused", above 128 clients, a
+    False entry) the clients are widened exactly into an fp32 bucket and the
+    fp32 passes run.  Either way the iterate is fp32 and the float keys come
+    back in the model's dtype, rounded once from the final fp32 chain.
+    Mixed-width float models are refused.
+
     fp32 models (integer buffers allowed, entering as fl32(v)).  Distances run
     over the weight keys; the result's weight keys are the last pass's z, and
     BatchNorm statistics and counters are the weighted sum with the same final
@@ -1323,7 +1354,17 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
         raise ValueError(f"the fused Weiszfeld kernel holds at most {GEOMED_MAX_CLIENTS} clients (K = {K})")
     _one_device(dicts[0], keys, "geomed")
     on_dev = dicts[0][keys[0]].is_cuda
-    bucket, dev = _float_bucket(dicts[0], K, "geomed", device)
+    # 16-bit rounds are taken from device-resident clients (the rows are laid
+    # out where the updates already are); host dicts of a 16-bit model stay
+    # refused by _float_bucket below, with its message
+    row16 = _geomed_row16(dicts[0][k].dtype for k in keys) if on_dev else None
+    if row16 is not None and K <= GEOMED_MAX_CLIENTS and \
+            (method == "fused" or (method == "auto" and geomed16_auto(row16, K))):
+        out, info = _geometric_median16(dicts, keys, row16, a, nu, maxiter, ftol, device)
+        return (out, info) if return_info else out
+    # a 16-bit model that does not take the 16-bit kernel is widened exactly
+    # into the fp32 bucket; anything else but fp32 is refused there
+    bucket, dev = _float_bucket(dicts[0], K, "geomed", device, widen=row16)
     fused = method == "fused" or (method == "auto" and geomed_auto_fused(K))
     with torch.cuda.device(dev):
         for i, d in enumerate(dicts):
@@ -1367,8 +1408,131 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
             w32 = [float(np.float32(w[i])) for i in alive]
             kn.wsum_ptrs(torch.float32, table(alive), kn.weights_for(w32, torch.float32, dev), len(alive), g.length,
                          row, True)
-        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+        if row16 is None:
+            out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+        else:  # the widened model's float keys: the fp32 row rounded once; integer keys stay fp32
+            is16 = {k: dicts[0][k].dtype == row16 for k in keys}
+            out = _rows_to_dict([(_subgroup(g, lambda k: is16[k]), kn.round_f32(row, row16)),
+                                 (_subgroup(g, lambda k: not is16[k]), row)], keys, on_dev, clone=True)
     return (out, info) if return_info else out
+
+
+# Whether "auto" runs the 16-bit fused kernel (fedagg_wsum_dist2_16) for a
+# bf16 / f16 model at the K tier (K <= tier), by GEOMED_AUTO_FUSED's rule
+# against the fp32 fused kernel on the widened copy of the same rows: True only
+# where the 16-bit pass's median time beat the fp32 pass's by more than the
+# larger min-max spread of the two at the full K and at a padded K of the tier
+# (tools/geomed16_probe.py -> profiles/geomed16_probe.json, NOTES.md §7b,
+# DESIGN.md).  A tier that did not win, or was not measured, is False, and
+# "auto" widens the clients into an fp32 bucket there.  Measured 2026-11-26 on
+# the tree that adds the kernel (parent commit f0c5841), one MI355X, 25,610,152
+# columns, the two launched alternately on the same rows, median of 10
+# (min - max) ms, 16-bit / fp32-on-the-widened-copy, full K then padded K:
+#   bf16   8: 0.122 (0.106 - 0.126) / 0.179 (0.174 - 0.183): gap 0.057 > 0.020;
+#             K = 6    0.121 (0.114 - 0.123) / 0.167 (0.163 - 0.170): gap 0.046 > 0.009
+#         16: 0.185 (0.175 - 0.193) / 0.322 (0.319 - 0.329): gap 0.136 > 0.018;
+#             K = 12   0.183 (0.179 - 0.185) / 0.273 (0.268 - 0.280): gap 0.090 > 0.012
+#         32: 0.342 (0.333 - 0.347) / 0.630 (0.627 - 0.638): gap 0.289 > 0.014;
+#             K = 24   0.326 (0.321 - 0.343) / 0.524 (0.522 - 0.530): gap 0.199 > 0.022
+#         64: 0.638 (0.628 - 0.650) / 1.196 (1.186 - 1.212): gap 0.557 > 0.026;
+#             K = 48   0.620 (0.613 - 0.627) / 1.004 (0.999 - 1.012): gap 0.384 > 0.014
+#        128: 1.254 (1.245 - 1.274) / 2.294 (2.279 - 2.340): gap 1.040 > 0.061;
+#             K = 100  1.533 (1.526 - 1.548) / 2.031 (2.021 - 2.052): gap 0.498 > 0.031
+#   f16    8: 0.115 / 0.173, gap 0.057 > 0.013; K = 6    0.119 / 0.162, gap 0.043 > 0.009
+#         16: 0.186 / 0.322, gap 0.136 > 0.018; K = 12   0.183 / 0.272, gap 0.089 > 0.039
+#         32: 0.344 / 0.630, gap 0.286 > 0.019; K = 24   0.333 / 0.525, gap 0.192 > 0.015
+#         64: 0.647 / 1.196, gap 0.549 > 0.021; K = 48   0.642 / 1.003, gap 0.361 > 0.017
+#        128: 1.261 / 2.292, gap 1.030 > 0.025; K = 100  1.574 / 2.041, gap 0.468 > 0.034
+# 1.82x - 1.87x at the full tiers from 32 clients, 1.47x - 1.74x at 8 and 16,
+# 1.30x - 1.62x at the padded K (K = 100 is slower than K = 128: 28 slots
+# re-read row 0 and the padded form holds two waves per SIMD, not three).  The
+# widening the fp32 path pays once per round (128 rows, a torch copy) took
+# 3.36 ms (3.33 - 3.38) and is not in the fp32 times above.
+GEOMED16_AUTO = {torch.bfloat16: {8: True, 16: True, 32: True, 64: True, 128: True},
+                 torch.float16: {8: True, 16: True, 32: True, 64: True, 128: True}}
+
+
+def geomed16_auto(dtype: torch.dtype, K: int) -> bool:
+    """Whether "auto" runs the 16-bit fused kernel for K clients of a bf16 /
+    f16 model (GEOMED16_AUTO)."""
+    return _tier_auto(GEOMED16_AUTO[dtype], GEOMED_MAX_CLIENTS, K)
+
+
+def _geomed_row16(dts) -> "torch.dtype | None":
+    """bf16 / f16 for a model whose float keys are all of that one dtype
+    (integer buffers allowed), else None: fp32 models, and the mixed-width
+    ones _float_bucket refuses."""
+    dts = set(dts)
+    for dt in _PAIR16_DT:
+        if dt in dts and dts <= {dt, torch.int64, torch.int32}:
+            return dt
+    return None
+
+
+def _subgroup(g, keep):
+    """The keys of row group g that `keep` accepts, as _rows_to_dict reads a
+    group."""
+    sel = [j for j, k in enumerate(g.keys) if keep(k)]
+    return types.SimpleNamespace(keys=[g.keys[j] for j in sel], offsets=[g.offsets[j] for j in sel],
+                                 numels=[g.numels[j] for j in sel], shapes=[g.shapes[j] for j in sel])
+
+
+def _geometric_median16(dicts, keys, row16: torch.dtype, a, nu: float, maxiter: int, ftol: float, device):
+    """geometric_median for an all-bf16 / all-f16 model of up to
+    GEOMED_MAX_CLIENTS clients on rows that stay 16-bit on the card (laid out
+    as coordinate_wise_trimmed_mean lays a 16-bit model out: the float keys'
+    16-bit row, integer buffers in an fp32 row as fl32(v)).  Every pass is one
+    fedagg_wsum_dist2_16 launch; the iterate is fp32 throughout.  The result
+    row is one fedagg_wsum_bf16 / _f16 pass in FEDAGG_ACC_FP32 mode with the
+    final weights: the same chain rounded once, rne(z) at the weight columns,
+    BatchNorm statistics with the same weights; the integer row one
+    fedagg_wsum_f32 pass.  -> (OrderedDict, GeomedInfo)"""
+    K = len(dicts)
+    t0 = dicts[0][keys[0]]
+    dev = t0.device if t0.is_cuda else (torch.device(device) if device is not None else
+                                        torch.device("cuda", torch.cuda.current_device()))
+    with torch.cuda.device(dev):
+        bucket = ClientBucket([(k, tuple(dicts[0][k].shape), dicts[0][k].dtype) for k in keys], K, dev)
+        for i, d in enumerate(dicts):
+            _put_float(bucket, i, d, keys)
+        bucket.sync_ingest()
+        g = bucket.groups[row16]
+        chunks, n_chunks = weight_chunks(g, nat.DIST_CHUNK, dev)
+        z = torch.zeros(g.padded, dtype=torch.float32, device=dev)
+        tables = {}
+
+        def table(gr, alive):
+            if len(alive) == K:
+                return gr.d_ptrs
+            if (gr.dtype, tuple(alive)) not in tables:
+                tables[(gr.dtype, tuple(alive))] = kn.upload_i64([gr.rows[i].data_ptr() for i in alive], dev)
+            return tables[(gr.dtype, tuple(alive))]
+
+        def make_step(alive):
+            ptrs, Ka = table(g, alive), len(alive)
+
+            def step(w32):
+                d_w = kn.weights_for(w32, torch.float32, dev)
+                return z, wsum_dist2_rows(ptrs, d_w, Ka, chunks, n_chunks, z, dev, dtype=row16).cpu().numpy()
+            return step
+
+        def norms2():
+            # torch ops, widened and summed in fp64 per segment: only after a non-finite pass 0
+            n2 = torch.zeros(K, dtype=torch.float64, device=dev)
+            for i in range(K):
+                for o, n in weight_segments(g):
+                    n2[i] += g.rows[i, o:o + n].double().square().sum()
+            return n2.cpu().numpy()
+
+        _, w, info, alive = geometric_median_screened(make_step, norms2, a, nu, maxiter, ftol)
+        info.method = "fused"
+        d_w = kn.weights_for([float(np.float32(w[i])) for i in alive], torch.float32, dev)
+        rows = []
+        for gr in bucket.groups.values():  # the 16-bit row rounded once from the fp32 chain; the integer keys' fp32 row
+            row = torch.empty(gr.padded, dtype=gr.dtype, device=dev)
+            kn.wsum_ptrs(gr.dtype, table(gr, alive), d_w, len(alive), gr.length, row, True, kn.ACC_FP32)
+            rows.append((gr, row))
+        return _rows_to_dict(rows, keys, t0.is_cuda, clone=True), info
 
 
 # ---- FLTrust (csrc/robust.hip: dotnorm2, wsum_diff) -----------------------------

@@ -648,6 +648,36 @@ int fedagg_wsum_dist2_f32(const float* const* d_src, const float* d_w, int32_t K
                           double* d_work, int64_t work_len,
                           uint32_t flags, fedagg_stream_t stream);
 
+/* fedagg_wsum_dist2_f32 for 1 <= K <= FEDAGG_GEOMED_MAX_CLIENTS rows of dtype
+ * FEDAGG_DT_BF16 or FEDAGG_DT_F16 (csrc/geomed16.hip): one pass over rows that
+ * stay 16-bit on the card.  Every element is widened to fp32 exactly when it
+ * is loaded; after that the operation is the fp32 kernel's:
+ *   d_z[e] (an fp32 row indexed by absolute column, touched only at table
+ *     columns): acc = fl32(x_0[e] * w_0); acc = fl32(acc + fl32(x_i[e] * w_i)),
+ *     two roundings per client, never an FMA: bit-identical to fedagg_wsum_f32
+ *     and fedagg_wsum_dist2_f32 on the widened copy of the rows, -0 columns,
+ *     fp32 denormals (a bf16 subnormal is an fp32 subnormal) and f16
+ *     subnormals (fp32 normals once widened) included.  The iterate is fp32:
+ *     nothing is rounded to 16 bits here, so it stays fp32 across passes.
+ *   d_dist2[i] = sum over the table columns of (double)fl32(x_i[e] - d_z[e])^2:
+ *     exact squares summed in fp64, in the kernel's own but fixed order
+ *     (per-block partials in d_work, a fixed-order finish, no atomics): two
+ *     calls on the same inputs give the same bits.
+ * The chunk table counts columns of the 16-bit rows ((start, length) pairs,
+ * 1 <= length <= FEDAGG_DIST_CHUNK, starts of any alignment).  A chunk whose
+ * start is even loads dwords (two columns a lane) when every row pointer is
+ * 4-byte aligned, and 2-byte elements otherwise; d_z is the same bits either
+ * way, and nothing outside the table's columns is read.  Workspace
+ * (fedagg_robust_work_len(FEDAGG_WORK_WSUM_DIST2, K, n_chunks), a smaller one
+ * accepted down to K doubles), flags (FEDAGG_HOST_WEIGHTS), n_chunks == 0
+ * (d_dist2 = 0, d_z untouched) and errors as fedagg_wsum_dist2_f32;
+ * FEDAGG_EINVAL also for any other dtype (checked first). */
+int fedagg_wsum_dist2_16(int32_t dtype, const void* const* d_src, const float* d_w, int32_t K,
+                         const int64_t* d_chunks, int64_t n_chunks,
+                         float* d_z, double* d_dist2,
+                         double* d_work, int64_t work_len,
+                         uint32_t flags, fedagg_stream_t stream);
+
 /* The clipped rebuild of NormDiffClippingDefense (:38-54): over the first N
  * columns of every row,
  *   d_dst_i[e] = fl32( fl32( fl32(src_i[e] - ref[e]) / d_div[i] ) + ref[e] )
