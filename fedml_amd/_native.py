@@ -93,6 +93,8 @@ SIGNATURES = {
     "fedagg_trimmed_mean_wide": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_nearmedian_mean_f32": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_nearmedian_mean_wide_f32": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _U32, _P]),
+    "fedagg_nearmedian_mean_16": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
+    "fedagg_nearmedian_mean_wide_16": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_sum_mod_i64": (ctypes.c_int, [_P, _I32, _I64, _I64, _P, _U32, _P]),
     "fedagg_lsa_reconstruct_f32": (ctypes.c_int, [_P, _I32, _I64, _P, _I64, _I32, _F, _P, _U32, _P]),
     "fedagg_host_pack": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32]),

@@ -71,7 +71,13 @@ that are pure reductions over the client axis.
                 one launch over the whole row up to 128 selected clients,
                 fedagg_nearmedian_mean_wide_f32 from 129 to 1024 in the tiers
                 of NEARMEDIAN_WIDE_AUTO, the same rule in torch ops above
-                that).  K >= 4f + 3.
+                that).  K >= 4f + 3.  An all-bf16 or all-f16 model, from host
+                or device dicts, stays 16-bit on the card: stage 1 on its rows
+                as Krum's (fedagg_pairdist2_16 / fedagg_pairgram2_16), stage 2
+                fedagg_nearmedian_mean_16 and fedagg_nearmedian_mean_wide_16
+                (the tiers of NEARMEDIAN_WIDE16_AUTO): the fp32 rule on the
+                exactly widened values, the mean rounded once to the model's
+                dtype; its integer buffers ride in an fp32 row of their own.
 
 "fltrust"       Not in FedML: FLTrust (Cao, Fang, Liu, Gong, NDSS 2021) under
                 our own specification (fltrust, fltrust_coeffs), the one rule
@@ -153,8 +159,10 @@ and multi-Krum take bf16 / f16 rows as they are (the differences of the exactly
 widened values, or the Gram about a centre rounded to the rows' dtype), like
 wise_median and wise_trimmed_mean; geomed takes all-bf16 / all-f16 models of
 device-resident clients too (the fused pass on 16-bit rows, or an exact widening into fp32 rows; an fp32
-iterate and one final rounding either way); wise_bulyan, fltrust,
-foolsgold_cos, cclip and norm_diff_clipping remain fp32-only.
+iterate and one final rounding either way); wise_bulyan takes all-bf16 /
+all-f16 models from host or device dicts (both stages on the 16-bit rows, the
+window's fp32 mean rounded once); fltrust, foolsgold_cos, cclip and
+norm_diff_clipping remain fp32-only.
 """
 from __future__ import annotations
 
@@ -2144,6 +2152,87 @@ def nearmedian_mean_rows_torch(rows, keep: int, chunk_cols: "int | None" = None)
     return out
 
 
+# ---- Bulyan's stage 2 on bf16 / f16 rows (csrc/nearmedian16.hip, nearmedian_wide16.hip)
+
+_NEAR16_DT = {torch.bfloat16: nat.DT_BF16, torch.float16: nat.DT_F16}
+
+
+def _nearmedian16(fn_name: str, what: str, d_ptrs: torch.Tensor, K: int, N: int, keep: int, out: torch.Tensor) -> None:
+    kn._require_cuda(out, what)
+    if out.dtype not in _NEAR16_DT:
+        raise TypeError(f"{what}: bf16 or f16 rows (got {out.dtype})")
+    nat.check(getattr(nat.lib(), fn_name)(_NEAR16_DT[out.dtype], d_ptrs.data_ptr(), K, N, keep, out.data_ptr(), 0,
+                                          nat.stream_handle()), what)
+
+
+def nearmedian_mean_rows16(d_ptrs: torch.Tensor, K: int, N: int, keep: int, out: torch.Tensor) -> None:
+    """nearmedian_mean_rows for K <= 128 device rows of out's dtype, bf16 or
+    f16 (fedagg_nearmedian_mean_16): every value widened exactly to fp32, the
+    fp32 operation on the widened values, the mean rounded once (nearest-even)
+    to the rows' dtype.  Rows and out are aligned to their element only."""
+    _nearmedian16("fedagg_nearmedian_mean_16", "nearmedian_mean_16", d_ptrs, K, N, keep, out)
+
+
+def nearmedian_mean_rows_wide16(d_ptrs: torch.Tensor, K: int, N: int, keep: int, out: torch.Tensor) -> None:
+    """nearmedian_mean_rows16's operation, bit for bit, for K <= 1024 bf16 or
+    f16 device rows (fedagg_nearmedian_mean_wide_16): the column spread over 4
+    or 8 lanes."""
+    _nearmedian16("fedagg_nearmedian_mean_wide_16", "nearmedian_mean_wide_16", d_ptrs, K, N, keep, out)
+
+
+# The tiers of the 16-bit wide kernel (theta <= tier) that bulyan hands to it
+# above 128 selected clients of a bf16 / f16 model, by NEARMEDIAN_WIDE_AUTO's
+# rule against nearmedian_mean_rows16_torch (tools/nearmedian16_probe.py ->
+# profiles/nearmedian16_probe.json, NOTES.md §5b): median of 10 alternating
+# launches on the same rows at 4,194,304 columns, at the full tier and a padded
+# K, the gap above the larger min-max spread.  An entry stays False until it
+# has been measured; such a tier takes the torch path.  Measured at keep =
+# K - 2 (K // 8), torch / kernel (bf16, f16; K = the full tier, then a padded
+# K); spreads under 0.16 ms for the kernel and under 9.6 ms for the torch
+# path, which is 116 ms to 1.98 s slower:
+#   tier  256: 85.3x, 86.5x (K = 256: 1.85 / 1.82 ms against 157 ms); 61.6x, 62.1x (K = 200)
+#   tier  512: 112.8x, 115.1x (K = 512: 4.58 / 4.46 ms against 517 / 513 ms); 61.9x, 61.8x (K = 384)
+#   tier 1024: 161.4x, 156.1x (K = 1024: 12.35 / 12.69 ms against 1.99 / 1.98 s); 82.9x, 83.5x (K = 700)
+# Beside the fp32 kernels on a widened copy of the same rows (which decides
+# nothing: that copy is what these kernels avoid) the 16-bit ones take 0.995x
+# to 1.13x the time in the wide tiers and 1.14x to 1.19x at K = 128 and 100.
+NEARMEDIAN_WIDE16_AUTO = {torch.bfloat16: {256: True, 512: True, 1024: True},
+                          torch.float16: {256: True, 512: True, 1024: True}}
+
+
+def nearmedian_wide16_auto(dtype: torch.dtype, theta: int) -> bool:
+    """Whether bulyan runs the 16-bit wide kernel for theta selected clients of
+    a `dtype` model above NEARMEDIAN_MAX_CLIENTS (NEARMEDIAN_WIDE16_AUTO)."""
+    return _tier_auto(NEARMEDIAN_WIDE16_AUTO[dtype], NEARMEDIAN_WIDE_MAX_CLIENTS, theta)
+
+
+def nearmedian_mean_rows16_torch(rows, keep: int, chunk_cols: "int | None" = None) -> torch.Tensor:
+    """The specification of fedagg_nearmedian_mean_16 in torch ops, on any
+    device and for any K: per column chunk the bf16 / f16 rows ((K, N) tensor
+    or list of K rows) are widened exactly, nearmedian_mean_rows_torch runs on
+    the widened chunk and its fp32 result is rounded once to the rows' dtype.
+    The path above 1024 selected clients and in the tiers that
+    NEARMEDIAN_WIDE16_AUTO leaves False.  chunk_cols: columns per chunk
+    (default: temporaries of about 1 GiB)."""
+    K = len(rows)
+    if K < 1:
+        raise ValueError("nearmedian mean of no rows")
+    if keep < 1 or keep > K:
+        raise ValueError(f"keep = {keep} of K = {K} rows")
+    r0 = rows[0]
+    if r0.dtype not in _NEAR16_DT:
+        raise TypeError(f"nearmedian_mean_16: bf16 or f16 rows (got {r0.dtype})")
+    N = r0.numel()
+    if chunk_cols is None:
+        chunk_cols = max(1, (1 << 30) // (36 * K))  # the fp32 path's temporaries and the widened chunk
+    out = torch.empty(N, dtype=r0.dtype, device=r0.device)
+    for c0 in range(0, N, chunk_cols):
+        c1 = min(N, c0 + chunk_cols)
+        x = rows[:, c0:c1] if isinstance(rows, torch.Tensor) else torch.stack([row[c0:c1] for row in rows])
+        out[c0:c1] = nearmedian_mean_rows_torch(x.float(), keep, chunk_cols).to(r0.dtype)
+    return out
+
+
 # bulyan_select sorts every row of the distances once above this many clients;
 # up to it the n x n sub-matrix is re-sorted in every round, which is as fast
 # there (NOTES.md, "Bulyan above 128 selected clients")
@@ -2317,10 +2406,20 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
     129 to 1024 selected clients (in the tiers of NEARMEDIAN_WIDE_AUTO) and
     nearmedian_mean_rows_torch for the rest.
 
-    fp32 models (integer buffers allowed, entering as fl32(v)).  Sample counts
-    are ignored, as by the median.  Returns a new OrderedDict in client 0's
-    key order on the inputs' device (integer keys come back fp32); no client
-    dict is modified.  return_info: also the BulyanInfo."""
+    fp32 models (integer buffers allowed, entering as fl32(v)), and all-bf16 or
+    all-f16 models, whose float keys stay one 16-bit row group on the card:
+    stage 1 is pairdist2_rows on those rows (method "gram_wide" is a
+    ValueError there), stage 2 fedagg_nearmedian_mean_16 /
+    fedagg_nearmedian_mean_wide_16 (in the tiers of NEARMEDIAN_WIDE16_AUTO) /
+    nearmedian_mean_rows16_torch: the fp32 operation on the exactly widened
+    values, rounded once to the model's dtype.  Their int64 / int32 / bool
+    buffers form an fp32 row group as fl32(v), reduced by the fp32 kernels
+    through the same selection; an integer tensor under a weight-key name is
+    refused (it would sit outside the distances' rows).  Mixed-width float
+    models are refused.  Sample counts are ignored, as by the median.  Returns
+    a new OrderedDict in client 0's key order on the inputs' device (float keys
+    in the model's dtype, integer keys fp32); no client dict is modified.
+    return_info: also the BulyanInfo."""
     f = byzantine_client_num
     K = len(raw_client_grad_list)
     if f < 0:
@@ -2336,28 +2435,64 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
         return (OrderedDict(), info) if return_info else OrderedDict()
     _one_device(dicts[0], keys, "wise_bulyan")
     on_dev = dicts[0][keys[0]].is_cuda
-    bucket, dev = _float_bucket(dicts[0], K, "wise_bulyan", device)
+    row_dt = _bulyan_row16(dicts[0], keys)
+    if row_dt is None:  # fp32 models; everything else is refused there, with its message
+        row_dt = torch.float32
+        bucket, dev = _float_bucket(dicts[0], K, "wise_bulyan", device)
+    else:
+        for k in keys:
+            if is_weight_param(k) and not dicts[0][k].is_floating_point():
+                raise NotImplementedError(
+                    f"wise_bulyan: key {k!r} is an integer tensor ({dicts[0][k].dtype}) under a weight-key name; in a "
+                    f"{row_dt} model the distances run over the {row_dt} rows, which it would not be part of")
+        t0 = dicts[0][keys[0]]
+        dev = t0.device if t0.is_cuda else (torch.device(device) if device is not None else
+                                            torch.device("cuda", torch.cuda.current_device()))
+        with torch.cuda.device(dev):
+            bucket = ClientBucket([(k, tuple(dicts[0][k].shape), dicts[0][k].dtype) for k in keys], K, dev)
     with torch.cuda.device(dev):
         for i, d in enumerate(dicts):
             _put_float(bucket, i, d, keys)
         bucket.sync_ingest()
-        g = bucket.groups[torch.float32]
+        g = bucket.groups[row_dt]  # the float keys: an fp32 model's only group
         if f == 0:
             selected, scores = bulyan_select(np.empty((K, 0)), 0)  # no distances needed
         else:
             chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
             D = pairdist2_rows(g.d_ptrs, K, chunks, n_chunks, dev, method, length=g.length,
-                               aligned=True).cpu().numpy()
+                               aligned=True, dtype=g.dtype).cpu().numpy()
             selected, scores = bulyan_select(D, f)
-        if theta <= NEARMEDIAN_MAX_CLIENTS or nearmedian_wide_auto(theta):
-            ptrs = g.d_ptrs if selected == list(range(K)) else \
-                kn.upload_i64([g.rows[i].data_ptr() for i in selected], dev)
-            row = torch.zeros(g.padded, dtype=torch.float32, device=dev)
-            if theta <= NEARMEDIAN_MAX_CLIENTS:
-                nearmedian_mean_rows(ptrs, theta, g.length, beta, row)
-            else:
-                nearmedian_mean_rows_wide(ptrs, theta, g.length, beta, row)
-        else:
-            row = nearmedian_mean_rows_torch([g.rows[i][:g.length] for i in selected], beta)
-        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+
+        def rows():  # a 16-bit model's integer buffers are a second, fp32 group: the same selection
+            for gg in bucket.groups.values():
+                yield gg, _bulyan_window(gg, selected, K, theta, beta, dev)
+
+        out = _rows_to_dict(rows(), keys, on_dev, clone=True)
     return (out, BulyanInfo(selected, scores, theta, beta, method)) if return_info else out
+
+
+def _bulyan_row16(d0, keys) -> "torch.dtype | None":
+    """bf16 / f16 for a model whose float keys are all of that one dtype
+    (int64 / int32 / bool buffers beside them); None for every other model."""
+    dts = {d0[k].dtype for k in keys}
+    floats = {dt for dt in dts if dt.is_floating_point}
+    if len(floats) == 1 and floats <= set(_NEAR16_DT) and dts - floats <= {torch.int64, torch.int32, torch.bool}:
+        return next(iter(floats))
+    return None
+
+
+def _bulyan_window(g, selected, K: int, theta: int, beta: int, dev) -> torch.Tensor:
+    """Stage 2 of bulyan on one row group (fp32, bf16 or f16): the finished row."""
+    if g.dtype in _NEAR16_DT:
+        narrow, wide, in_torch = nearmedian_mean_rows16, nearmedian_mean_rows_wide16, nearmedian_mean_rows16_torch
+        wide_auto = nearmedian_wide16_auto(g.dtype, theta)
+    else:
+        narrow, wide, in_torch = nearmedian_mean_rows, nearmedian_mean_rows_wide, nearmedian_mean_rows_torch
+        wide_auto = nearmedian_wide_auto(theta)
+    if theta <= NEARMEDIAN_MAX_CLIENTS or wide_auto:
+        ptrs = g.d_ptrs if selected == list(range(K)) else \
+            kn.upload_i64([g.rows[i].data_ptr() for i in selected], dev)
+        row = torch.zeros(g.padded, dtype=g.dtype, device=dev)
+        (narrow if theta <= NEARMEDIAN_MAX_CLIENTS else wide)(ptrs, theta, g.length, beta, row)
+        return row
+    return in_torch([g.rows[i][:g.length] for i in selected], beta)

@@ -475,6 +475,53 @@ int fedagg_nearmedian_mean_wide_f32(const float* const* d_src, int32_t K,
                                     int64_t N, int32_t keep, float* d_out,
                                     uint32_t flags, fedagg_stream_t stream);
 
+/* The mean of the values nearest the median over K bf16 or f16 rows
+ * (csrc/nearmedian16.hip; dtype FEDAGG_DT_BF16 or FEDAGG_DT_F16, d_src and
+ * d_out of that dtype): stage 2 of "wise_bulyan" for a 16-bit model whose
+ * rows stay 16-bit on the card.  The result is defined through
+ * fedagg_nearmedian_mean_f32 above: every value is widened exactly to fp32 and
+ * steps 1-6 are applied to the widened values as they stand:
+ *   - the total order, with every NaN counted and standing as +inf above the
+ *     real +inf;
+ *   - m = s[(K-1)/2];
+ *   - d(v) = 0 when v == m, otherwise fl32(|v - m|), an fp32 subtraction: a
+ *     difference that rounds in fp32 (the smallest f16 subnormal beside the
+ *     largest f16 value) or overflows to +inf in fp32 (the largest bf16 values
+ *     of both signs) does so here too, and the ties that follow go LEFT;
+ *   - the window by the two-pointer rule;
+ *   - the sequential fp32 chain in ascending rank from s[lo];
+ *   - the IEEE division by fl32(keep);
+ *   - a NaN when the window reaches a NaN.
+ * The fp32 result is then rounded once, round-to-nearest-even, to the rows'
+ * dtype.  So out == round(fedagg_nearmedian_mean_f32(widened rows)), bit for
+ * bit, except for which NaN bit pattern comes back.  The mean is not one of
+ * the inputs: it can overflow the dtype to +-inf, as the rounding gives.
+ * fedagg_nearmedian_mean_f32's kernel form on 2-byte elements (K tiers
+ * 8 .. 128, launches of 2^30 columns); rows and output are aligned to their
+ * element only, one form for every alignment.  Stream-ordered; allocates
+ * nothing and does not synchronise; flags is reserved.  Checked before any
+ * HIP call: FEDAGG_EINVAL for K < 1, N < 0, keep < 1, keep > K, a null pointer
+ * or another dtype; FEDAGG_ENOKERNEL for K > FEDAGG_NEARMEDIAN_MAX_CLIENTS;
+ * N == 0 returns FEDAGG_OK without a launch. */
+int fedagg_nearmedian_mean_16(int32_t dtype, const void* const* d_src, int32_t K,
+                              int64_t N, int32_t keep, void* d_out,
+                              uint32_t flags, fedagg_stream_t stream);
+
+/* fedagg_nearmedian_mean_16's operation, bit for bit, for up to 1024 bf16 or
+ * f16 rows (csrc/nearmedian_wide16.hip): fedagg_nearmedian_mean_wide_f32's
+ * form (4 x 64 up to 256 rows, 4 x 128 up to 512, 8 x 128 up to 1024) on
+ * 2-byte elements widened as they arrive; the partners' LDS ring holds fp32
+ * words.  Accepts 1 <= K <= FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS.  One launch,
+ * for every alignment; stream-ordered, allocates nothing, does not
+ * synchronise; flags is reserved.  FEDAGG_EINVAL for K < 1, N < 0, keep < 1,
+ * keep > K, a null pointer, another dtype or N beyond 2^31 - 1 blocks;
+ * FEDAGG_ENOKERNEL for K > FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS.  N == 0 is
+ * FEDAGG_OK without a launch. */
+int fedagg_nearmedian_mean_wide_16(int32_t dtype, const void* const* d_src,
+                                   int32_t K, int64_t N, int32_t keep,
+                                   void* d_out, uint32_t flags,
+                                   fedagg_stream_t stream);
+
 /* Distance-based defenses (csrc/robust.hip).  Rows are K fp32 device
  * pointers; the columns that count (FedML's vectorize_weight: every key but
  * BatchNorm running stats and counters, core/security/common/utils.py:8-21)
