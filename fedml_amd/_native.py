@@ -30,6 +30,7 @@ WORK_PAIRGRAM_WIDE = 4  # FEDAGG_WORK_PAIRGRAM_WIDE
 WORK_DOTNORM2 = 5  # FEDAGG_WORK_DOTNORM2
 WORK_HISTGRAM = 8  # FEDAGG_WORK_HISTGRAM (6 and 7 are unassigned)
 WSUM_DIFF_TILE = 2048  # FEDAGG_WSUM_DIFF_TILE: columns a block of fedagg_wsum_diff_f32 works at a time
+WSUM_DIFF16_TILE = 4096  # FEDAGG_WSUM_DIFF16_TILE: the same of fedagg_wsum_diff_16
 PAIRGRAM_WIDE_MAX_CLIENTS = 1024  # FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS
 TRIMMED_MAX_CLIENTS = 128  # FEDAGG_TRIMMED_MAX_CLIENTS
 TRIMMED_WIDE_MAX_CLIENTS = 1024  # FEDAGG_TRIMMED_WIDE_MAX_CLIENTS
@@ -115,6 +116,8 @@ SIGNATURES = {
     "fedagg_scale_diff_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "fedagg_dotnorm2_f32": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_wsum_diff_f32": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _P]),
+    "fedagg_dotnorm2_16": (ctypes.c_int, [_I32, _P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),
+    "fedagg_wsum_diff_16": (ctypes.c_int, [_I32, _P, _P, _I32, _P, _I64, _P, _P]),
     "fedagg_histgram_f32": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_last_error": (ctypes.c_char_p, []),
     "fedagg_version": (_I32, []),

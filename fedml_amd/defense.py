@@ -91,7 +91,11 @@ that are pure reductions over the client axis.
                 (fedagg_dotnorm2_f32: exact products, fp64 sums, one read),
                 then global + sum c_i (x_i - global) over EVERY key for the
                 trusted clients only (fedagg_wsum_diff_f32); 2(K + 1) doubles
-                on the host in between.  Any number of clients.
+                on the host in between.  Any number of clients.  An all-bf16
+                or all-f16 model of device-resident clients stays 16-bit on
+                the card (fedagg_dotnorm2_16, fedagg_wsum_diff_16: the same
+                operations on the exactly widened values, the result rounded
+                once); its integer buffers ride in an fp32 row of their own.
 
 "foolsgold_cos" Not FedML's "foolsgold" (which stays refused: its source is not
                 mirrored here): FoolsGold (Fung, Yoon, Beschastnikh) under our
@@ -161,7 +165,9 @@ wise_median and wise_trimmed_mean; geomed takes all-bf16 / all-f16 models of
 device-resident clients too (the fused pass on 16-bit rows, or an exact widening into fp32 rows; an fp32
 iterate and one final rounding either way); wise_bulyan takes all-bf16 /
 all-f16 models from host or device dicts (both stages on the 16-bit rows, the
-window's fp32 mean rounded once); fltrust, foolsgold_cos, cclip and
+window's fp32 mean rounded once); fltrust takes all-bf16 / all-f16 models of
+device-resident clients (fedagg_dotnorm2_16 and fedagg_wsum_diff_16 on the
+16-bit rows, the rebuild's fp32 chain rounded once); foolsgold_cos, cclip and
 norm_diff_clipping remain fp32-only.
 """
 from __future__ import annotations
@@ -1543,71 +1549,92 @@ def _geometric_median16(dicts, keys, row16: torch.dtype, a, nu: float, maxiter: 
         return _rows_to_dict(rows, keys, t0.is_cuda, clone=True), info
 
 
-# ---- FLTrust (csrc/robust.hip: dotnorm2, wsum_diff) -----------------------------
+# ---- FLTrust (csrc/robust.hip: dotnorm2, wsum_diff; csrc/fltrust16.hip: the 16-bit pair) ----
+
+_FLTRUST16_DT = {torch.bfloat16: nat.DT_BF16, torch.float16: nat.DT_F16}
+
 
 def dotnorm2_rows(d_ptrs: torch.Tensor, K: int, ref: torch.Tensor, direction: torch.Tensor, chunks: torch.Tensor,
                   n_chunks: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(dot, n2): for K fp32 device rows, the fp64 inner products of x_i - ref
-    with direction - ref and the fp64 squared norms of x_i - ref over the
-    chunked columns, in one read of the rows (fedagg_dotnorm2_f32).  Two views
-    of one 2K-double device tensor."""
+    """(dot, n2): for K device rows, the fp64 inner products of x_i - ref with
+    direction - ref and the fp64 squared norms of x_i - ref over the chunked
+    columns, in one read of the rows.  fp32 rows: fedagg_dotnorm2_f32; bf16 /
+    f16 rows (the rows' dtype is ref's): fedagg_dotnorm2_16, the same sums of
+    the exactly widened values.  TypeError unless ref and direction share one
+    of the three dtypes.  Two views of one 2K-double device tensor."""
     kn._require_cuda(ref, "dotnorm2")
-    if ref.dtype != torch.float32 or direction.dtype != torch.float32:
-        raise TypeError("dotnorm2: fp32 rows")
+    if ref.dtype != direction.dtype or (ref.dtype != torch.float32 and ref.dtype not in _FLTRUST16_DT):
+        raise TypeError(f"dotnorm2: fp32, bf16 or f16 rows of one dtype (ref {ref.dtype}, direction {direction.dtype})")
     out = torch.empty(2 * K, dtype=torch.float64, device=device)
     work = _work(nat.WORK_DOTNORM2, K, n_chunks, device)
-    nat.check(nat.lib().fedagg_dotnorm2_f32(d_ptrs.data_ptr(), K, ref.data_ptr(), direction.data_ptr(),
-                                            chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(),
-                                            work.numel(), nat.stream_handle()), "dotnorm2")
+    tail = (ref.data_ptr(), direction.data_ptr(), chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(),
+            work.numel(), nat.stream_handle())
+    if ref.dtype == torch.float32:
+        nat.check(nat.lib().fedagg_dotnorm2_f32(d_ptrs.data_ptr(), K, *tail), "dotnorm2")
+    else:
+        nat.check(nat.lib().fedagg_dotnorm2_16(_FLTRUST16_DT[ref.dtype], d_ptrs.data_ptr(), K, *tail), "dotnorm2_16")
     return out[:K], out[K:]
 
 
 def wsum_diff_rows(d_ptrs: "torch.Tensor | None", d_c: "torch.Tensor | None", K: int, ref: torch.Tensor, N: int,
                    out: torch.Tensor) -> None:
-    """out[:N] = ref + the chain of c_i (x_i - ref) over K fp32 device rows
-    (fedagg_wsum_diff_f32; K == 0: out = ref, no table needed).  d_c: K device
-    floats.  out aliases no input."""
+    """out[:N] = ref + the chain of c_i (x_i - ref) over K device rows (K == 0:
+    out = ref, no table needed).  fp32 rows: fedagg_wsum_diff_f32; bf16 / f16
+    rows (the rows' dtype is ref's): fedagg_wsum_diff_16, the fp32 chain on the
+    exactly widened values, rounded once to that dtype.  d_c: K device floats
+    either way.  TypeError unless ref and out share one of the three dtypes.
+    out aliases no input."""
     kn._require_cuda(out, "wsum_diff")
-    if ref.dtype != torch.float32 or out.dtype != torch.float32:
-        raise TypeError("wsum_diff: fp32 rows and output")
-    nat.check(nat.lib().fedagg_wsum_diff_f32(d_ptrs.data_ptr() if K > 0 else None, d_c.data_ptr() if K > 0 else None,
-                                             K, ref.data_ptr(), N, out.data_ptr(), nat.stream_handle()), "wsum_diff")
+    if ref.dtype != out.dtype or (ref.dtype != torch.float32 and ref.dtype not in _FLTRUST16_DT):
+        raise TypeError(f"wsum_diff: fp32, bf16 or f16 rows and output of one dtype (ref {ref.dtype}, out {out.dtype})")
+    args = (d_ptrs.data_ptr() if K > 0 else None, d_c.data_ptr() if K > 0 else None, K, ref.data_ptr(), N,
+            out.data_ptr(), nat.stream_handle())
+    if ref.dtype == torch.float32:
+        nat.check(nat.lib().fedagg_wsum_diff_f32(*args), "wsum_diff")
+    else:
+        nat.check(nat.lib().fedagg_wsum_diff_16(_FLTRUST16_DT[ref.dtype], *args), "wsum_diff_16")
 
 
 def dotnorm2_rows_torch(rows, ref, direction, cols=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The specification of fedagg_dotnorm2_f32 in torch ops, on any device.
-    rows: a (K, N) fp32 tensor or a list of K rows; cols: index tensor of the
-    columns that count (None: all).  Returns (dot, n2), K float64 each: the
-    fp64 sums of the exact products of the fp32 differences a_i = x_i - ref
-    with b = direction - ref, and of a_i with itself (torch's own summation
-    order: equal to the kernel's up to fp64 rounding, not bit for bit)."""
+    """The specification of fedagg_dotnorm2_f32 / fedagg_dotnorm2_16 in torch
+    ops, on any device.  rows: a (K, N) tensor or a list of K rows, fp32, or
+    bf16 / f16 (widened exactly first, ref and direction with them); cols:
+    index tensor of the columns that count (None: all).  Returns (dot, n2), K
+    float64 each: the fp64 sums of the exact products of the fp32 differences
+    a_i = x_i - ref with b = direction - ref, and of a_i with itself (torch's
+    own summation order: equal to the kernel's up to fp64 rounding, not bit
+    for bit)."""
     K = len(rows)
     dev = ref.device
+    ref, direction = ref.float(), direction.float()
     rc = ref if cols is None else ref[cols]
     b = ((direction if cols is None else direction[cols]) - rc).double()
     dot = torch.empty(K, dtype=torch.float64, device=dev)
     n2 = torch.empty(K, dtype=torch.float64, device=dev)
     for i in range(K):
-        a = ((rows[i] if cols is None else rows[i][cols]) - rc).double()
+        a = ((rows[i] if cols is None else rows[i][cols]).float() - rc).double()
         dot[i] = (a * b).sum()
         n2[i] = (a * a).sum()
     return dot, n2
 
 
 def wsum_diff_rows_torch(rows, c32, ref) -> torch.Tensor:
-    """The specification of fedagg_wsum_diff_f32 in torch ops, on any device:
-    acc = fl(c_0 fl(x_0 - ref)), acc = fl(acc + fl(c_i fl(x_i - ref))) client by
-    client, ref + acc at the end; ref itself (a copy) for no rows.  c32: K
-    coefficients (rounded to fp32 here).  Separate mul and add, each rounded
-    once, as the kernel's."""
+    """The specification of fedagg_wsum_diff_f32 / fedagg_wsum_diff_16 in torch
+    ops, on any device: acc = fl(c_0 fl(x_0 - ref)), acc = fl(acc + fl(c_i
+    fl(x_i - ref))) client by client, ref + acc at the end; ref itself (a
+    copy) for no rows.  c32: K coefficients (rounded to fp32 here).  Separate
+    mul and add, each rounded once, as the kernel's.  bf16 / f16 rows (ref's
+    dtype) are widened exactly, the chain is fp32 and its result is rounded
+    once to that dtype."""
     K = len(rows)
     if K == 0:
         return ref.clone()
+    dt, ref = ref.dtype, ref.float()
     c = torch.tensor([float(v) for v in c32], dtype=torch.float64).to(torch.float32).to(ref.device)
-    acc = (rows[0] - ref) * c[0]
+    acc = (rows[0].float() - ref) * c[0]
     for i in range(1, K):
-        acc = acc + (rows[i] - ref) * c[i]
-    return ref + acc
+        acc = acc + (rows[i].float() - ref) * c[i]
+    return (ref + acc).to(dt)
 
 
 def fltrust_coeffs(dot, n2, nb2, lr: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
@@ -1684,9 +1711,20 @@ def fltrust(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mode
     are never read.  No trusted client (S == 0): a warning, and the result is g.
 
     fp32 models (integer buffers allowed, entering as fl32(v) and coming back
-    fp32).  KeyError for a key of client 0 missing from another client, from
-    global_model or from root_model; ValueError when the root update is zero or
-    not finite.  Returns a new OrderedDict in client 0's key order on the
+    fp32), and all-bf16 or all-f16 models of device-resident clients, whose
+    float keys stay one 16-bit row group on the card: the cosines are one
+    fedagg_dotnorm2_16 pass over those rows and the rebuild one
+    fedagg_wsum_diff_16 pass, the fp32 operations on the exactly widened
+    values, the result rounded once to the model's dtype.  Their int64 / int32
+    / bool buffers form an fp32 row group as fl32(v), rebuilt by
+    fedagg_wsum_diff_f32 with the same coefficients over the same trusted
+    clients (float keys come back in the model's dtype, integer keys fp32); an
+    integer tensor under a weight-key name is refused (it would sit outside
+    the cosines' rows), and so is a global or root model whose key dtypes
+    differ from client 0's (TypeError).  Host dicts of a 16-bit model and
+    mixed-width float models are refused.  KeyError for a key of client 0
+    missing from another client, from global_model or from root_model;
+    ValueError when the root update is zero or not finite.  Returns a new OrderedDict in client 0's key order on the
     inputs' device; no input is modified.  return_info: also the FLTrustInfo."""
     K = len(raw_client_grad_list)
     if K < 1:
@@ -1700,8 +1738,25 @@ def fltrust(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mode
         return (OrderedDict(), info) if return_info else OrderedDict()
     _one_device(dicts[0], keys, "fltrust")
     on_dev = dicts[0][keys[0]].is_cuda
-    bucket, dev = _float_bucket(dicts[0], K, "fltrust", device)
-    gb, _ = _float_bucket(dicts[0], 2, "fltrust", dev)  # the global and the root model, laid out like the clients
+    row_dt = _bulyan_row16(dicts[0], keys) if on_dev else None
+    if row_dt is None:  # fp32 models; everything else is refused there, with its message
+        row_dt = torch.float32
+        bucket, dev = _float_bucket(dicts[0], K, "fltrust", device)
+        gb, _ = _float_bucket(dicts[0], 2, "fltrust", dev)  # the global and the root model, laid out like the clients
+    else:
+        for k in keys:
+            if is_weight_param(k) and not dicts[0][k].is_floating_point():
+                raise NotImplementedError(
+                    f"fltrust: key {k!r} is an integer tensor ({dicts[0][k].dtype}) under a weight-key name; in a "
+                    f"{row_dt} model the distances run over the {row_dt} rows, which it would not be part of")
+            for name, m in (("global_model", global_model), ("root_model", root_model)):
+                if m[k].dtype != dicts[0][k].dtype:  # put() would round an fp32 model into the 16-bit row
+                    raise TypeError(f"fltrust: {name}[{k!r}] is {m[k].dtype}, client 0's is {dicts[0][k].dtype}; in a "
+                                    f"{row_dt} round the global and the root model have the clients' dtypes")
+        dev = dicts[0][keys[0]].device
+        layout = [(k, tuple(dicts[0][k].shape), dicts[0][k].dtype) for k in keys]
+        with torch.cuda.device(dev):
+            bucket, gb = ClientBucket(layout, K, dev), ClientBucket(layout, 2, dev)
     with torch.cuda.device(dev):
         for i, d in enumerate(dicts):
             _put_float(bucket, i, d, keys)
@@ -1709,7 +1764,7 @@ def fltrust(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mode
         _put_float(gb, 1, root_model, keys)
         bucket.sync_ingest()
         gb.sync_ingest()
-        g, gg = bucket.groups[torch.float32], gb.groups[torch.float32]
+        g, gg = bucket.groups[row_dt], gb.groups[row_dt]  # the float keys: an fp32 model's only group
         ref, root = gg.rows[0], gg.rows[1]
         chunks, n_chunks = weight_chunks(g, nat.DIST_CHUNK, dev)
         ptrs = kn.upload_i64([g.rows[i].data_ptr() for i in range(K)] + [root.data_ptr()], dev)
@@ -1725,12 +1780,17 @@ def fltrust(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mode
         if not trusted:
             logging.warning("fltrust: no client's update has a positive cosine with the root update; "
                             "the global model is kept")
-        row = torch.empty(g.padded, dtype=torch.float32, device=dev)
         Kt = len(trusted)
-        t_ptrs = kn.upload_i64([g.rows[i].data_ptr() for i in trusted], dev) if Kt else None
         d_c = kn.upload_f32([float(c32[i]) for i in trusted], dev) if Kt else None
-        wsum_diff_rows(t_ptrs, d_c, Kt, ref, g.length, row)
-        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+
+        def rows():  # a 16-bit model's integer buffers are a second, fp32 group: the same coefficients
+            for dt, gr in bucket.groups.items():
+                row = torch.empty(gr.padded, dtype=dt, device=dev)
+                t_ptrs = kn.upload_i64([gr.rows[i].data_ptr() for i in trusted], dev) if Kt else None
+                wsum_diff_rows(t_ptrs, d_c, Kt, gb.groups[dt].rows[0], gr.length, row)
+                yield gr, row
+
+        out = _rows_to_dict(rows(), keys, on_dev, clone=True)
     info = FLTrustInfo(cos, trust, c32.astype(np.float64), trusted, nb)
     return (out, info) if return_info else out
 

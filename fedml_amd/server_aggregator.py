@@ -125,7 +125,15 @@ class ServerAggregator(ABC):
         """The server's root model for the coming round of the "fltrust"
         defense: the state dict the server's own local training on its clean
         root data gave, started from the current global model.  Not FedML's
-        interface (FLTrust is ours); one aggregate() uses it up."""
+        interface (FLTrust is ours); one aggregate() uses it up.
+
+        A bf16 / f16 round: dfn.fltrust keeps an all-bf16 or all-f16 model
+        16-bit on the card when the CLIENTS' dicts are device tensors; the
+        global model comes from get_model_params(), which hands over the
+        model's own tensors where the model lives (host tensors with
+        cpu_transfer, and in the subclasses that call model.cpu()), and may
+        sit on either side, as may this root model.  Client dicts of host
+        tensors are refused for a 16-bit model, as before."""
         self._fltrust_root = model_params
 
     def set_foolsgold_clients(self, client_ids) -> None:

@@ -796,6 +796,51 @@ int fedagg_wsum_diff_f32(const float* const* d_src, const float* d_c, int32_t K,
                          const float* d_ref, int64_t N, float* d_out,
                          fedagg_stream_t stream);
 
+/* The same two passes for rows of dtype FEDAGG_DT_BF16 or FEDAGG_DT_F16
+ * (csrc/fltrust16.hip): the rows stay 16-bit on the card and every element is
+ * widened to fp32 exactly when it is used.  FEDAGG_EINVAL for any other dtype
+ * (checked first).
+ *
+ * fedagg_dotnorm2_16: d_src's K rows, d_ref and d_dir are all of `dtype`.
+ * fedagg_dotnorm2_f32's operation on the widened values:
+ * a_i[e] = fl32(src_i[e] - d_ref[e]) and b[e] = fl32(d_dir[e] - d_ref[e]), one
+ * rounded fp32 subtraction each, d_out[i] = sum_e (double)a_i[e] (double)b[e]
+ * and d_out[K + i] = sum_e (double)a_i[e]^2, exact products summed in fp64 in
+ * the kernel's own but fixed order: the exact sums up to fp64 rounding, the
+ * same bits from call to call and at every alignment of the rows; not bit for
+ * bit the fp32 kernel's sums on a widened copy (another summation order).
+ * Row j = d_dir gives d_out[j] and d_out[K + j] the same bits.  The chunk
+ * table counts columns of the 16-bit rows ((start, length) pairs, 1 <= length
+ * <= FEDAGG_DIST_CHUNK, starts of any alignment; a column outside the table is
+ * not read).  A row whose chunk begins on a 16-byte boundary (a 16-byte
+ * aligned pointer and a start that is a multiple of 8) is read with 16-byte
+ * loads, every other row, and a ragged chunk end, with 2-byte loads.
+ * Workspace (FEDAGG_WORK_DOTNORM2: 2 K min(n_chunks, 1024) doubles, a smaller
+ * one accepted down to 2 K), n_chunks == 0 (d_out = 0; a kernel, not a
+ * memset) and the other errors as fedagg_dotnorm2_f32.
+ *
+ * fedagg_wsum_diff_16: the rows, d_ref and d_out are of `dtype`; d_c stays K
+ * device floats.  fedagg_wsum_diff_f32's fp32 chain on the widened values
+ *   acc = fl32(d_c[0] * fl32(src_0[e] - d_ref[e]))
+ *   acc = fl32(acc + fl32(d_c[i] * fl32(src_i[e] - d_ref[e])))   i = 1 .. K - 1
+ *   d_out[e] = round_dtype(fl32(d_ref[e] + acc))
+ * never an FMA, the result rounded once to `dtype`, nearest even (overflow to
+ * +-inf, NaN stays NaN).  K == 0: d_out[e] = d_ref[e].  d_out aliases no
+ * input.  Rows, d_ref and d_out may have any 2-byte alignment: a pointer that
+ * is 16-byte aligned is accessed with 16-byte vectors (eight columns), any
+ * other with 2-byte accesses, decided per pointer in the kernel; a ragged last
+ * tile takes the bounded 2-byte accesses.  A block works
+ * FEDAGG_WSUM_DIFF16_TILE columns at a time; columns are indexed in 64 bits.
+ * N == 0 and the other errors as fedagg_wsum_diff_f32. */
+#define FEDAGG_WSUM_DIFF16_TILE 4096
+int fedagg_dotnorm2_16(int32_t dtype, const void* const* d_src, int32_t K, const void* d_ref,
+                       const void* d_dir, const int64_t* d_chunks,
+                       int64_t n_chunks, double* d_out /* 2K */, double* d_work,
+                       int64_t work_len, fedagg_stream_t stream);
+int fedagg_wsum_diff_16(int32_t dtype, const void* const* d_src, const float* d_c, int32_t K,
+                        const void* d_ref, int64_t N, void* d_out,
+                        fedagg_stream_t stream);
+
 /* The fused pass of the "foolsgold_cos" defense (FoolsGold: Fung, Yoon,
  * Beschastnikh; ours, specified at fedml_amd.defense.foolsgold; FedML's own
  * "foolsgold" is not reproduced).  csrc/histgram.hip.  For every column e of
