@@ -112,6 +112,7 @@ SIGNATURES = {
     "fedagg_pairdist2_16": (ctypes.c_int, [_I32, _P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_pairgram2_16": (ctypes.c_int, [_I32, _P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_pairgram2_wide_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
+    "fedagg_pairgram2_wide_16": (ctypes.c_int, [_I32, _P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_clip_diff_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "fedagg_scale_diff_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "fedagg_dotnorm2_f32": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),

@@ -693,6 +693,85 @@ __global__ __launch_bounds__(256) void gram_dist_kernel(const double* __restrict
   D[e] = i == j ? 0.0 : (d < 0.0 ? 0.0 : d);
 }
 
+// ---------------------------------------------------------------------------
+// What the 16-bit Grams share (robust16.hip, pairgram_wide16.hip).
+
+// four columns of a row as loaded (two packed 16-bit pairs) -> fp32, exactly
+template <class T>
+__device__ __forceinline__ f32x4 widen4(u32x2v r) {
+  if constexpr (std::is_same_v<T, bf16_t>) return f32x4{bf16_lo(r.x), bf16_hi(r.x), bf16_lo(r.y), bf16_hi(r.y)};
+  return f32x4{widen_f16(r.x & 0xffffu), widen_f16(r.x >> 16), widen_f16(r.y & 0xffffu), widen_f16(r.y >> 16)};
+}
+
+// fp32 -> the nearest value of the rows' dtype (ties to even), as fp32
+template <class T>
+__device__ __forceinline__ f32x4 round_dt4(f32x4 r) {
+  if constexpr (std::is_same_v<T, bf16_t>) {
+    const uint32_t a = pk_bf16(r.x, r.y), b = pk_bf16(r.z, r.w);
+    return f32x4{bf16_lo(a), bf16_hi(a), bf16_lo(b), bf16_hi(b)};
+  }
+  return f32x4{float(_Float16(r.x)), float(_Float16(r.y)), float(_Float16(r.z)), float(_Float16(r.w))};
+}
+
+// Ends a plane-count branch: 8 wait states between the branch's last MFMA and
+// whatever follows the join.  No wrong value was ever observed without it.  It
+// is there for tools/mfma_hazards.py, whose rule is conservative (every
+// instruction counts one wait state, and the hardware's own interlock is not
+// modelled): the three branches leave the accumulators in registers of their
+// own choice, and by that count the moves that reunite them (NB = 2, 3) came 7
+// states after the MFMA that wrote their source, one short of the 8 the rule
+// asks before a VALU read.  One s_nop 7 per stage and wave keeps every shipped
+// build inside the rule instead of arguing an exception to it.
+template <int N>
+__device__ __forceinline__ void mfma_settle(f32x4v (&a)[N]) {
+  static_assert(N >= 1 && N <= 5, "one operand per accumulator");
+  if constexpr (N == 1) asm volatile("s_nop 7" : "+v"(a[0]));
+  if constexpr (N == 2) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]));
+  if constexpr (N == 3) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]));
+  if constexpr (N == 4) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+  if constexpr (N == 5) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]));
+}
+
+// ---------------------------------------------------------------------------
+// What the wide (tile-pair) Grams share: pairgram_wide_kernel (robust.hip,
+// which describes the decomposition) and pairgram_wide16_kernel
+// (pairgram_wide16.hip).
+constexpr int kWideMax = FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS;
+constexpr int kWideBS = 512;
+constexpr int kWidePlane = 2 * kPT * kSplitRB;  // a plane: tile I's 64 rows, then tile J's
+constexpr int kWideBlocks = 2048;               // blocks the grid aims for (one per CU resident)
+// a diagonal pair's tiles per wave: {A group, first B group, tiles}; waves w
+// and w + 4 sit on one SIMD
+[[maybe_unused]] __constant__ constexpr int kWideDiag[8][3] = {{0, 0, 2}, {1, 1, 2}, {2, 2, 2}, {1, 3, 1},
+                                                               {0, 2, 1}, {0, 3, 1}, {0, 0, 0}, {3, 3, 1}};
+
+// M (K x K, fp64, both triangles) = the tile pairs' partials summed over the
+// chunk groups (gram_sum_kernel's order).  A block owns 64 entries of one
+// 16 x 16 group-tile; a diagonal pair's tiles a > b do not exist and come from
+// their mirrors.
+[[maybe_unused]] __global__ __launch_bounds__(256) void gram_wide_sum_kernel(const double* __restrict__ partial,
+                                                                             int G, int K, double* __restrict__ M) {
+  __shared__ double quarter[4][64];
+  const int T = (K + kPT - 1) / kPT;
+  const int64_t E = int64_t(T * (T + 1) / 2) * (kPT * kPT);
+  const int lane = threadIdx.x & 63, qq = threadIdx.x >> 6;
+  const int e = blockIdx.x * 64 + lane;
+  const int2 tile = tile_of(e >> 12, T);
+  const int a = (e >> 10) & 3, b = (e >> 8) & 3;
+  const bool dg = tile.x == tile.y;
+  if (dg && a > b) return;  // block-uniform
+  const double v = quartered_sum(partial + e, E, G, quarter, lane, qq);
+  if (qq != 0) return;
+  const int row = tile.x * kPT + 16 * a + ((e >> 4) & 15), col = tile.y * kPT + 16 * b + (e & 15);
+  if (row >= K || col >= K) return;
+  M[int64_t(row) * K + col] = v;  // a diagonal group-tile writes both orders itself
+  if (!(dg && a == b)) M[int64_t(col) * K + row] = v;
+}
+
+// grid_groups' blocks per group that make a wide kernel's grid about
+// kWideBlocks blocks (grid_groups aims for 4096)
+[[maybe_unused]] int wide_group_blocks(int NT) { return NT * (4096 / kWideBlocks); }
+
 int grid_groups(int per_group_blocks, int64_t n_chunks, int64_t work_len, int64_t per_group_work) {
   int64_t G = (4096 + per_group_blocks - 1) / per_group_blocks;
   if (G > n_chunks) G = n_chunks;

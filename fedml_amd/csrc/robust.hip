@@ -545,15 +545,8 @@ __global__ __launch_bounds__(kSplit8BS, 1) void pairgram_split8_kernel(const flo
 // an XCD-grouped block order did not change the time (NOTES.md 5c).
 // Partials: [g][tile pair][16 group-tiles a * 4 + b][16 x 16]; a diagonal pair
 // writes the slots a <= b only and gram_wide_sum_kernel reads no other.
-constexpr int kWideMax = FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS;
-constexpr int kWideBS = 512;
-constexpr int kWidePlane = 2 * kPT * kSplitRB;  // a plane: tile I's 64 rows, then tile J's
-constexpr int kWideBlocks = 2048;               // blocks the grid aims for (one per CU resident)
-// a diagonal pair's tiles per wave: {A group, first B group, tiles}; waves w
-// and w + 4 sit on one SIMD
-__constant__ constexpr int kWideDiag[8][3] = {{0, 0, 2}, {1, 1, 2}, {2, 2, 2}, {1, 3, 1},
-                                              {0, 2, 1}, {0, 3, 1}, {0, 0, 0}, {3, 3, 1}};
-
+// (kWideBS, kWidePlane, kWideDiag, gram_wide_sum_kernel and wide_group_blocks
+// are in pairdist.h: pairgram_wide16.hip's kernel for 16-bit rows shares them.)
 __global__ __launch_bounds__(kWideBS, 1) void pairgram_wide_kernel(const float* const* __restrict__ src, int K,
                                                                    const float* __restrict__ center,
                                                                    const int64_t* __restrict__ chunks,
@@ -704,29 +697,6 @@ __global__ __launch_bounds__(kWideBS, 1) void pairgram_wide_kernel(const float* 
       for (int r = 0; r < 4; ++r) out[(4 * q + r) * 16 + i16] = acc64[j][r];
     }
   }
-}
-
-// M (K x K, fp64, both triangles) = the tile pairs' partials summed over the
-// chunk groups (gram_sum_kernel's order).  A block owns 64 entries of one
-// 16 x 16 group-tile; a diagonal pair's tiles a > b do not exist and come from
-// their mirrors.
-__global__ __launch_bounds__(256) void gram_wide_sum_kernel(const double* __restrict__ partial, int G, int K,
-                                                            double* __restrict__ M) {
-  __shared__ double quarter[4][64];
-  const int T = (K + kPT - 1) / kPT;
-  const int64_t E = int64_t(T * (T + 1) / 2) * (kPT * kPT);
-  const int lane = threadIdx.x & 63, qq = threadIdx.x >> 6;
-  const int e = blockIdx.x * 64 + lane;
-  const int2 tile = tile_of(e >> 12, T);
-  const int a = (e >> 10) & 3, b = (e >> 8) & 3;
-  const bool dg = tile.x == tile.y;
-  if (dg && a > b) return;  // block-uniform
-  const double v = quartered_sum(partial + e, E, G, quarter, lane, qq);
-  if (qq != 0) return;
-  const int row = tile.x * kPT + 16 * a + ((e >> 4) & 15), col = tile.y * kPT + 16 * b + (e & 15);
-  if (row >= K || col >= K) return;
-  M[int64_t(row) * K + col] = v;  // a diagonal group-tile writes both orders itself
-  if (!(dg && a == b)) M[int64_t(col) * K + row] = v;
 }
 
 // ---------------------------------------------------------------------------
@@ -899,10 +869,6 @@ __global__ __launch_bounds__(kBS) void wsum_diff_kernel(const float* const* __re
 }
 
 constexpr int kWdMaxBlocks = 1 << 20;  // tiles above that (N > 2^31 columns) go round the grid
-
-// grid_groups' blocks per group that make pairgram_wide_kernel's grid about
-// kWideBlocks blocks (grid_groups aims for 4096)
-int wide_group_blocks(int NT) { return NT * (4096 / kWideBlocks); }
 
 template <bool MUL>
 int launch_diff(const char* what, const float* const* d_src, int32_t K, const float* d_ref, const float* d_c, int64_t N,

@@ -61,41 +61,7 @@
 
 namespace {
 
-// four columns of a row as loaded (two packed 16-bit pairs) -> fp32, exactly
-template <class T>
-__device__ __forceinline__ f32x4 widen4(u32x2v r) {
-  if constexpr (std::is_same_v<T, bf16_t>) return f32x4{bf16_lo(r.x), bf16_hi(r.x), bf16_lo(r.y), bf16_hi(r.y)};
-  return f32x4{widen_f16(r.x & 0xffffu), widen_f16(r.x >> 16), widen_f16(r.y & 0xffffu), widen_f16(r.y >> 16)};
-}
-
-// fp32 -> the nearest value of the rows' dtype (ties to even), as fp32
-template <class T>
-__device__ __forceinline__ f32x4 round_dt4(f32x4 r) {
-  if constexpr (std::is_same_v<T, bf16_t>) {
-    const uint32_t a = pk_bf16(r.x, r.y), b = pk_bf16(r.z, r.w);
-    return f32x4{bf16_lo(a), bf16_hi(a), bf16_lo(b), bf16_hi(b)};
-  }
-  return f32x4{float(_Float16(r.x)), float(_Float16(r.y)), float(_Float16(r.z)), float(_Float16(r.w))};
-}
-
-// Ends a plane-count branch: 8 wait states between the branch's last MFMA and
-// whatever follows the join.  No wrong value was ever observed without it.  It
-// is there for tools/mfma_hazards.py, whose rule is conservative (every
-// instruction counts one wait state, and the hardware's own interlock is not
-// modelled): the three branches leave the accumulators in registers of their
-// own choice, and by that count the moves that reunite them (NB = 2, 3) came 7
-// states after the MFMA that wrote their source, one short of the 8 the rule
-// asks before a VALU read.  One s_nop 7 per stage and wave keeps every shipped
-// build inside the rule instead of arguing an exception to it.
-template <int N>
-__device__ __forceinline__ void mfma_settle(f32x4v (&a)[N]) {
-  static_assert(N >= 1 && N <= 5, "one operand per accumulator");
-  if constexpr (N == 1) asm volatile("s_nop 7" : "+v"(a[0]));
-  if constexpr (N == 2) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]));
-  if constexpr (N == 3) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]));
-  if constexpr (N == 4) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
-  if constexpr (N == 5) asm volatile("s_nop 7" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]));
-}
+// widen4, round_dt4 and mfma_settle are in pairdist.h (pairgram_wide16.hip shares them)
 
 template <class T, int NB>
 __global__ __launch_bounds__(kSplit8BS, 1) void pairgram16_kernel(const T* const* __restrict__ src, int K,

@@ -73,7 +73,8 @@ that are pure reductions over the client axis.
                 of NEARMEDIAN_WIDE_AUTO, the same rule in torch ops above
                 that).  K >= 4f + 3.  An all-bf16 or all-f16 model, from host
                 or device dicts, stays 16-bit on the card: stage 1 on its rows
-                as Krum's (fedagg_pairdist2_16 / fedagg_pairgram2_16), stage 2
+                as Krum's (fedagg_pairdist2_16 / fedagg_pairgram2_16 /
+                fedagg_pairgram2_wide_16), stage 2
                 fedagg_nearmedian_mean_16 and fedagg_nearmedian_mean_wide_16
                 (the tiers of NEARMEDIAN_WIDE16_AUTO): the fp32 rule on the
                 exactly widened values, the mean rounded once to the model's
@@ -121,8 +122,11 @@ that are pure reductions over the client axis.
                 the centred Gram on the matrix cores: fedagg_pairgram2_f32 up
                 to 128 clients, fedagg_pairgram2_wide_f32 from 129 to 1024).
                 An all-bf16 or all-f16 model stays 16-bit on the card:
-                fedagg_pairdist2_16, or fedagg_pairgram2_16 up to 128 clients
-                where PAIRGRAM16_AUTO measured it faster; a mixed-width float
+                fedagg_pairdist2_16, fedagg_pairgram2_16 up to 128 clients
+                where PAIRGRAM16_AUTO measured it faster, or the tile-pair
+                Gram fedagg_pairgram2_wide_16 from 129 to 1024 ("gram_wide"
+                always, "auto" in the tiers of PAIRGRAM_WIDE16_AUTO); a
+                mixed-width float
                 model is widened exactly into fp32 rows;
                 the scores (sum of the K - f - 2 smallest; in numpy above 128
                 clients, bit for bit the reference's loop), their fp32 argsort
@@ -652,16 +656,59 @@ def pairgram_wide_auto(K: int) -> bool:
 # Gram on the widened copy the 16-bit Gram is level, 0.94x - 1.07x: it saves the
 # fp32 copy, not time.
 PAIRGRAM16_AUTO = {torch.bfloat16: True, torch.float16: True}
+# The K tiers (K <= tier) in which pairdist2_rows' "auto" runs the 16-bit wide
+# Gram (fedagg_pairgram2_wide_16) above 128 clients of that dtype, by
+# PAIRGRAM_WIDE_AUTO's rule: a tier is True only if the wide Gram's median time,
+# ITS CENTRE PASS INCLUDED, is below the 16-bit exact kernel's (what "auto" ran
+# before) by more than the larger min-max spread of the two, at the tier's full
+# K and at its padded K (256 / 200, 512 / 384, 1024 / 700).  An unmeasured tier
+# is False.  tools/pairgram_wide16_probe.py -> profiles/pairgram_wide16_probe.json.
+# Measured at 4,194,304 columns of base + small-update rows, the paths launched
+# alternately on the same rows, median of 10 (min - max), exact / wide Gram;
+# gap = exact - wide Gram > larger spread:
+#   bf16 tier  256: K = 256  7.25 (7.15 - 7.70) / 4.02 (3.98 - 4.12) ms: gap 3.22 > 0.55;
+#                   K = 200  7.09 (7.02 - 7.21) / 3.89 (3.86 - 3.92): gap 3.20 > 0.19
+#        tier  512: K = 512  26.46 (26.29 - 26.68) / 14.56 (14.52 - 14.58): gap 11.90 > 0.39;
+#                   K = 384  15.75 (15.19 - 15.94) / 8.44 (8.38 - 8.53): gap 7.31 > 0.75
+#        tier 1024: K = 1024 97.44 (96.96 - 98.15) / 53.16 (53.00 - 53.43): gap 44.28 > 1.18;
+#                   K = 700  48.19 (47.67 - 48.59) / 26.43 (26.26 - 26.57): gap 21.76 > 0.92
+#   f16  tier  256: K = 256  7.49 (7.34 - 7.55) / 4.55 (4.47 - 4.63): gap 2.94 > 0.22;
+#                   K = 200  7.33 (7.22 - 7.36) / 4.35 (4.33 - 4.39): gap 2.98 > 0.14
+#        tier  512: K = 512  26.87 (26.55 - 27.27) / 16.03 (16.01 - 16.09): gap 10.84 > 0.72;
+#                   K = 384  15.97 (15.86 - 16.13) / 9.31 (9.23 - 9.43): gap 6.66 > 0.27
+#        tier 1024: K = 1024 99.69 (98.93 - 100.56) / 59.01 (58.85 - 59.36): gap 40.68 > 1.63;
+#                   K = 700  48.97 (48.63 - 49.32) / 29.03 (28.90 - 29.16): gap 19.95 > 0.69
+# (1.8x - 1.9x for bf16, 1.65x - 1.7x for f16; the centre pass, 0.3 - 1.5 ms,
+# is inside the wide Gram's time.)  It does NOT beat the fp32 wide Gram on the
+# widened copy of the same rows, centre pass included: 0.92x - 0.97x of its
+# speed for bf16 and 0.83x - 0.88x for f16 (K = 1024: 53.16 / 59.01 ms against
+# 49.14 / 49.21).  It saves the fp32 copy, not time.  The plane count is worth
+# about 1 % here: scattered-exponent bf16 rows (P = 3 in every stage) take 14.73
+# (14.60 - 14.95) ms at K = 512 against 14.56 for P = 1, so the kernel is not
+# bound by its MFMAs (NOTES.md 5c).
+PAIRGRAM_WIDE16_AUTO = {torch.bfloat16: {256: True, 512: True, 1024: True},
+                        torch.float16: {256: True, 512: True, 1024: True}}
+
+
+def pairgram_wide16_auto(K: int, dtype: torch.dtype) -> bool:
+    """Whether pairdist2_rows' "auto" runs the 16-bit wide Gram for K clients
+    of `dtype` above GRAM_MAX_CLIENTS (PAIRGRAM_WIDE16_AUTO)."""
+    return _tier_auto(PAIRGRAM_WIDE16_AUTO[dtype], PAIRGRAM_WIDE_MAX_CLIENTS, K)
 _PAIR16_DT = {torch.bfloat16: nat.DT_BF16, torch.float16: nat.DT_F16}
 
 
-def client_mean_row(d_ptrs: torch.Tensor, K: int, length: int, device, aligned: bool = False) -> torch.Tensor:
-    """The mean of K fp32 device rows over their first `length` columns: one
-    pass of the FedAvg kernel with device weights 1/K (the wide Gram's centre).
+def client_mean_row(d_ptrs: torch.Tensor, K: int, length: int, device, aligned: bool = False,
+                    dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The mean of K device rows of `dtype` over their first `length` columns,
+    as a row of that dtype: one pass of the FedAvg kernel with device weights
+    1/K (the wide Gram's centre).  bf16 / f16 rows: the reference chain's
+    client order with an fp32 accumulator, rounded ONCE to the rows' dtype
+    (FEDAGG_ACC_FP32; rounding after every client would stall the sum of 1024
+    small terms), which is the rounded centre of fedagg_pairgram2_wide_16.
     aligned: every row is 16-byte aligned (the kernel's vector path)."""
-    out = torch.empty(max(length, 1), dtype=torch.float32, device=device)
+    out = torch.empty(max(length, 1), dtype=dtype, device=device)
     d_w = torch.full((K,), 1.0 / K, dtype=torch.float32, device=device)
-    kn.wsum_ptrs(torch.float32, d_ptrs, d_w, K, length, out, aligned)
+    kn.wsum_ptrs(dtype, d_ptrs, d_w, K, length, out, aligned, kn.ACC_FP32)
     return out
 
 
@@ -690,29 +737,48 @@ def pairdist2_rows(d_ptrs: torch.Tensor, K: int, chunks: torch.Tensor, n_chunks:
     bf16 / f16 rows (csrc/robust16.hip): "exact" is fedagg_pairdist2_16 (the
     same kernels on rows widened exactly as they load, any K); "gram" is
     fedagg_pairgram2_16 (K <= 128: the centre rounded to the rows' dtype, one
-    to six MFMA products per stage as its values need); "gram_wide" is a
-    ValueError; "auto" runs the Gram up to 128 clients where PAIRGRAM16_AUTO
-    says so, with the same gram_condition fallback to the 16-bit exact kernel
-    (bit for bit its result), and the exact kernel elsewhere.  `length`,
-    `center` and `aligned` serve the wide Gram's centre pass only and are
-    ignored for 16-bit rows: the 16-bit Gram forms its centre per stage and
-    checks alignment in the kernel."""
+    to six MFMA products per stage as its values need); "gram_wide" is
+    fedagg_pairgram2_wide_16 (csrc/pairgram_wide16.hip, K <= 1024: the same
+    plane count per stage and tile pair), centred on `center`, a device row OF
+    THE ROWS' DTYPE (TypeError otherwise), or, when center is None, on the
+    mean of the rows' first `length` columns rounded once to that dtype
+    (client_mean_row); "auto" runs the Gram up to 128 clients where
+    PAIRGRAM16_AUTO says so and the wide Gram from 129 to 1024 in the tiers of
+    PAIRGRAM_WIDE16_AUTO when a length or a centre is given, both with the
+    gram_condition fallback to the 16-bit exact kernel (bit for bit its
+    result), and the exact kernel elsewhere.  `length`, `center` and `aligned`
+    serve the wide Gram only: the narrow 16-bit Gram forms its centre per
+    stage, and both check alignment in the kernel."""
     if method not in ("auto", "gram", "gram_wide", "exact"):
         raise ValueError(f"pair distance method {method!r}: 'auto', 'gram', 'gram_wide' or 'exact'")
     if dtype != torch.float32 and dtype not in _PAIR16_DT:
         raise TypeError(f"pair distances: fp32, bf16 or f16 rows (got {dtype})")
     if dtype in _PAIR16_DT:
-        if method == "gram_wide":
-            raise ValueError("the wide Gram pair kernel takes fp32 rows only")
         gram = method == "gram" or (method == "auto" and K <= GRAM_MAX_CLIENTS and PAIRGRAM16_AUTO[dtype])
         if gram and K > GRAM_MAX_CLIENTS:
             raise ValueError(f"the Gram pair kernel holds at most {GRAM_MAX_CLIENTS} clients (K = {K})")
+        wide = method == "gram_wide" or (method == "auto" and K > GRAM_MAX_CLIENTS and pairgram_wide16_auto(K, dtype)
+                                         and (length is not None or center is not None))
+        if wide and K > PAIRGRAM_WIDE_MAX_CLIENTS:
+            raise ValueError(f"the wide Gram pair kernel holds at most {PAIRGRAM_WIDE_MAX_CLIENTS} clients (K = {K})")
+        if wide and center is None and length is None:  # before anything touches d_ptrs or the device
+            raise ValueError("pair distance method 'gram_wide' needs the rows' length or a centre row")
         out = torch.empty((K, K), dtype=torch.float64, device=device)
-        work = _work(nat.WORK_PAIRGRAM if gram else nat.WORK_PAIRDIST2, K, n_chunks, device)
-        fn = nat.lib().fedagg_pairgram2_16 if gram else nat.lib().fedagg_pairdist2_16
-        nat.check(fn(_PAIR16_DT[dtype], d_ptrs.data_ptr(), K, chunks.data_ptr(), n_chunks, out.data_ptr(),
-                     work.data_ptr(), work.numel(), nat.stream_handle()), "pairgram2_16" if gram else "pairdist2_16")
-        if gram and method == "auto" and gram_condition(out.cpu().numpy()) > GRAM_MAX_CONDITION:
+        if wide:
+            if center is None:
+                center = client_mean_row(d_ptrs, K, length, device, aligned, dtype)
+            elif center.dtype != dtype or not center.is_cuda:
+                raise TypeError(f"pair distance centre: a {dtype} device row, the rows' dtype")
+            work = _work(nat.WORK_PAIRGRAM_WIDE, K, n_chunks, device)
+            nat.check(nat.lib().fedagg_pairgram2_wide_16(_PAIR16_DT[dtype], d_ptrs.data_ptr(), K, center.data_ptr(),
+                                                         chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(),
+                                                         work.numel(), nat.stream_handle()), "pairgram2_wide_16")
+        else:
+            work = _work(nat.WORK_PAIRGRAM if gram else nat.WORK_PAIRDIST2, K, n_chunks, device)
+            fn = nat.lib().fedagg_pairgram2_16 if gram else nat.lib().fedagg_pairdist2_16
+            nat.check(fn(_PAIR16_DT[dtype], d_ptrs.data_ptr(), K, chunks.data_ptr(), n_chunks, out.data_ptr(),
+                         work.data_ptr(), work.numel(), nat.stream_handle()), "pairgram2_16" if gram else "pairdist2_16")
+        if (gram or wide) and method == "auto" and gram_condition(out.cpu().numpy()) > GRAM_MAX_CONDITION:
             return pairdist2_rows(d_ptrs, K, chunks, n_chunks, device, "exact", dtype=dtype)
         return out
     gram = method == "gram" or (method == "auto" and K <= GRAM_MAX_CLIENTS)
@@ -2468,8 +2534,8 @@ def bulyan(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], byzantine_cl
 
     fp32 models (integer buffers allowed, entering as fl32(v)), and all-bf16 or
     all-f16 models, whose float keys stay one 16-bit row group on the card:
-    stage 1 is pairdist2_rows on those rows (method "gram_wide" is a
-    ValueError there), stage 2 fedagg_nearmedian_mean_16 /
+    stage 1 is pairdist2_rows on those rows (method "gram_wide" is
+    fedagg_pairgram2_wide_16 there), stage 2 fedagg_nearmedian_mean_16 /
     fedagg_nearmedian_mean_wide_16 (in the tiers of NEARMEDIAN_WIDE16_AUTO) /
     nearmedian_mean_rows16_torch: the fp32 operation on the exactly widened
     values, rounded once to the model's dtype.  Their int64 / int32 / bool

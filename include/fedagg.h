@@ -663,6 +663,42 @@ int fedagg_pairgram2_wide_f32(const float* const* d_src, int32_t K,
                               int64_t n_chunks, double* d_out, double* d_work,
                               int64_t work_len, fedagg_stream_t stream);
 
+/* fedagg_pairgram2_wide_f32 for rows of dtype FEDAGG_DT_BF16 or FEDAGG_DT_F16
+ * (csrc/pairgram_wide16.hip), 1 <= K <= FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS: the
+ * same tile pairs, grid, partials ([g][tile pair][16 group-tiles][16 x 16]),
+ * K x K tail and finish, with fedagg_pairgram2_16's stage front.
+ *   c_i[e] = fl32(widen(src_i[e]) - widen(d_center[e])),   G = C C^T,
+ *   d_out[i*K + j] = max(0, G_ii + G_jj - (G_ij + G_ji)).
+ * d_center is one device row OF THE ROWS' DTYPE, indexed by absolute column
+ * like the client rows (any alignment; only the table's columns are read); it
+ * must not be null.  Every centre is correct (D is translation invariant) and
+ * decides conditioning only: |error| ~ 1e-7 (|c_i|^2 + |c_j|^2) about the
+ * centre used.  Callers pass the client mean rounded once to the rows' dtype
+ * (one fedagg_wsum_bf16 / fedagg_wsum_f16 pass with weights 1/K): x and the
+ * centre are then values of one format and, for clients that are a base plus
+ * small updates, c is a value of that format too, a bf16 from bf16 rows and at
+ * most 11 bits from f16 rows.  Per 64-column stage and per block (tile pair)
+ * the kernel multiplies only the bf16 planes of c = h + m + l that are there:
+ * hh alone, or hh, hm, mh, mm (all exact), or the six products of
+ * fedagg_pairgram2_f32; a stage with a non-finite c runs all six.  A stage
+ * takes 8-byte loads when its row pointers and d_center are 8-byte aligned
+ * and its first column is a multiple of 4, element loads otherwise.  fp32
+ * over 4 stages, fp64 across.  Guarantees as fedagg_pairgram2_wide_f32: d_out
+ * is exactly symmetric, 0 on the diagonal, never negative, NaN / inf pass
+ * through.  Deterministic: per-block partials in d_work, combined in a fixed
+ * order.  d_work: fedagg_robust_work_len(FEDAGG_WORK_PAIRGRAM_WIDE, K,
+ * n_chunks) doubles; a smaller one is accepted down to one chunk group's
+ * 4,096 doubles per 64 x 64 tile pair plus the K x K matrix and runs fewer
+ * chunk groups.  n_chunks == 0: d_out = 0.  Stream-ordered; allocates nothing
+ * and does not synchronise.  FEDAGG_EINVAL (checked before any HIP call) for a
+ * dtype other than the two, K < 1, K > 1024, n_chunks < 0, a null d_src,
+ * d_center or d_out, a null d_chunks or d_work with n_chunks > 0, or a
+ * workspace below that minimum. */
+int fedagg_pairgram2_wide_16(int32_t dtype, const void* const* d_src, int32_t K,
+                             const void* d_center, const int64_t* d_chunks,
+                             int64_t n_chunks, double* d_out, double* d_work,
+                             int64_t work_len, fedagg_stream_t stream);
+
 /* One Weiszfeld iteration of the geometric-median defense ("geomed";
  * csrc/geomed.hip) in ONE pass over the K fp32 rows: the weighted sum z of
  * the rows and every row's squared distance to z.  Only the columns of the
