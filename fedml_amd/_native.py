@@ -29,12 +29,14 @@ WORK_DIST2, WORK_PAIRDIST2, WORK_PAIRGRAM, WORK_WSUM_DIST2 = 0, 1, 2, 3
 WORK_PAIRGRAM_WIDE = 4  # FEDAGG_WORK_PAIRGRAM_WIDE
 WORK_DOTNORM2 = 5  # FEDAGG_WORK_DOTNORM2
 WORK_HISTGRAM = 8  # FEDAGG_WORK_HISTGRAM (6 and 7 are unassigned)
+WORK_WSUM_DIST2_WIDE = 9  # FEDAGG_WORK_WSUM_DIST2_WIDE
 WSUM_DIFF_TILE = 2048  # FEDAGG_WSUM_DIFF_TILE: columns a block of fedagg_wsum_diff_f32 works at a time
 WSUM_DIFF16_TILE = 4096  # FEDAGG_WSUM_DIFF16_TILE: the same of fedagg_wsum_diff_16
 PAIRGRAM_WIDE_MAX_CLIENTS = 1024  # FEDAGG_PAIRGRAM_WIDE_MAX_CLIENTS
 TRIMMED_MAX_CLIENTS = 128  # FEDAGG_TRIMMED_MAX_CLIENTS
 TRIMMED_WIDE_MAX_CLIENTS = 1024  # FEDAGG_TRIMMED_WIDE_MAX_CLIENTS
 GEOMED_MAX_CLIENTS = 128  # FEDAGG_GEOMED_MAX_CLIENTS
+GEOMED_WIDE_MAX_CLIENTS = 1024  # FEDAGG_GEOMED_WIDE_MAX_CLIENTS
 NEARMEDIAN_MAX_CLIENTS = 128  # FEDAGG_NEARMEDIAN_MAX_CLIENTS
 NEARMEDIAN_WIDE_MAX_CLIENTS = 1024  # FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS
 # FEDAGG_FEDOPT_*: the launch kinds of fedagg_wsum_fedopt_batch (besides the FEDAGG_OPT_* codes)
@@ -107,6 +109,8 @@ SIGNATURES = {
     "fedagg_dist2_f32": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_wsum_dist2_f32": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _U32, _P]),
     "fedagg_wsum_dist2_16": (ctypes.c_int, [_I32, _P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _U32, _P]),
+    "fedagg_wsum_dist2_wide_f32": (ctypes.c_int, [_P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _U32, _P]),
+    "fedagg_wsum_dist2_wide_16": (ctypes.c_int, [_I32, _P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _U32, _P]),
     "fedagg_pairdist2_f32": (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_pairgram2_f32": (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_pairdist2_16": (ctypes.c_int, [_I32, _P, _I32, _P, _I64, _P, _P, _I64, _P]),

@@ -41,6 +41,7 @@
 
 extern "C" int64_t fedagg_wsum_dist2_work_len_internal(int32_t K, int64_t n_chunks);
 extern "C" int64_t fedagg_histgram_work_len_internal(int32_t K, int64_t n_chunks);
+extern "C" int64_t fedagg_wsum_dist2_wide_work_len_internal(int32_t K, int64_t n_chunks);
 
 namespace {
 
@@ -911,6 +912,7 @@ int64_t fedagg_robust_work_len(int32_t kind, int32_t K, int64_t n_chunks) {
     return int64_t(NT) * grid_groups(wide_group_blocks(NT), n_chunks, 0, 0) * (kPT * kPT) + int64_t(K) * K;
   }
   if (kind == FEDAGG_WORK_WSUM_DIST2) return fedagg_wsum_dist2_work_len_internal(K, n_chunks);  // geomed.hip
+  if (kind == FEDAGG_WORK_WSUM_DIST2_WIDE) return fedagg_wsum_dist2_wide_work_len_internal(K, n_chunks);  // geomed_wide.hip
   if (kind == FEDAGG_WORK_DOTNORM2) return int64_t(2) * K * grid_groups(4, n_chunks, 0, 0);  // dist2's grid, two rows a client
   if (kind == FEDAGG_WORK_HISTGRAM) return fedagg_histgram_work_len_internal(K, n_chunks);  // histgram.hip
   return -1;

@@ -51,7 +51,11 @@ that are pure reductions over the client axis.
                 they load, an fp32 iterate, the result rounded once), which
                 "fused" always does and "auto" where GEOMED16_AUTO measured it
                 faster; elsewhere the clients are widened exactly into fp32
-                rows and the result is rounded once.  FedML's own
+                rows and the result is rounded once.  method="fused_wide"
+                keeps one pass per iteration for 129 to 1024 clients
+                (fedagg_wsum_dist2_wide_f32 / _16: a column held by 2, 4 or 8
+                lanes), 16-bit rows staying 16-bit with no fp32 copy of the
+                clients; "auto" does not take it.  FedML's own
                 "geometric_median" / "RFA" loop (a Python set of weights, a
                 truncating zip) is NOT reproduced: those names stay refused.
 
@@ -1181,6 +1185,25 @@ class RobustLearningRateDefense:
 # ---- geometric median (csrc/geomed.hip) ----------------------------------------
 
 GEOMED_MAX_CLIENTS = nat.GEOMED_MAX_CLIENTS  # fedagg_wsum_dist2_f32 holds up to 128 clients
+GEOMED_WIDE_MAX_CLIENTS = nat.GEOMED_WIDE_MAX_CLIENTS  # fedagg_wsum_dist2_wide_f32 / _16: up to 1024
+# "auto" does not take the wide kernel; what would decide it, by GEOMED_AUTO_FUSED's
+# rule (tools/geomed_wide_probe.py -> profiles/geomed_wide_probe.json, NOTES.md
+# 7b).  Measured 2026-11-26 on the tree that adds the kernel (parent commit
+# 52e4d65), one MI355X, 4,194,304 columns, wide kernel / weiszfeld_step_unfused
+# (on the widened copy for 16-bit rows) launched alternately, median of 10 ms,
+# full K then padded K:
+#   fp32  256: 0.972 / 1.390, gap 0.418 > 0.100;  K = 200  0.987 / 1.077, gap 0.090 > 0.065: wins
+#         512: 2.712 / 2.801, gap 0.089 < 0.136;  K = 384  2.429 / 2.086: loses
+#        1024: 9.805 / 5.548;                     K = 700  7.498 / 3.809: loses
+#   bf16  256: 0.557 / 1.411, gap 0.855 > 0.051;  K = 200  0.639 / 1.075, gap 0.436 > 0.030: wins
+#         512: 1.575 / 2.798, gap 1.223 > 0.112;  K = 384  1.482 / 2.084, gap 0.602 > 0.088: wins
+#        1024: 5.666 / 5.557;                     K = 700  4.407 / 3.808: loses
+#   f16   256: 0.565 / 1.402, gap 0.837 > 0.085;  K = 200  0.656 / 1.084, gap 0.428 > 0.031: wins
+#         512: 1.649 / 2.814, gap 1.166 > 0.052;  K = 384  1.526 / 2.115, gap 0.589 > 0.080: wins
+#        1024: 6.090 / 5.542;                     K = 700  4.622 / 3.847: loses
+# The 1024 tier is bound by VALU issue (8 phases of 128 dependent adds a
+# column).  The widening the pair pays once per round for 1024 16-bit rows took
+# 4.42 ms and is not in its times.
 # a client whose squared norm over the weight columns exceeds this (or is not
 # finite) is dropped by the screen: what is left has every |value| <= 2^126, so
 # every |z| <= 2^126 and no fp32 difference x - z can overflow
@@ -1252,6 +1275,36 @@ def wsum_dist2_rows(d_ptrs: torch.Tensor, d_w, K: int, chunks: torch.Tensor, n_c
     else:
         nat.check(nat.lib().fedagg_wsum_dist2_16(_PAIR16_DT[dtype], *a), "wsum_dist2_16")
     return out
+
+
+def wsum_dist2_rows_wide(d_ptrs: torch.Tensor, d_w, K: int, chunks: torch.Tensor, n_chunks: int, z: torch.Tensor,
+                         device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """wsum_dist2_rows for up to GEOMED_WIDE_MAX_CLIENTS clients
+    (fedagg_wsum_dist2_wide_f32 / _16: a column held by a group of 2, 4 or 8
+    lanes): the same z, bit for bit, and the same distances.  The kernel takes
+    device weights only, so a kernels.HostWeights is uploaded here."""
+    kn._require_cuda(z, "wsum_dist2_wide")
+    if z.dtype != torch.float32:
+        raise TypeError("wsum_dist2_wide: fp32 output")
+    if dtype != torch.float32 and dtype not in _PAIR16_DT:
+        raise TypeError(f"wsum_dist2_wide: fp32, bf16 or f16 rows (got {dtype})")
+    if isinstance(d_w, kn.HostWeights):
+        d_w = kn.upload_f32(list(d_w.buf)[:K], device)
+    out = torch.empty(K, dtype=torch.float64, device=device)
+    work = _work(nat.WORK_WSUM_DIST2_WIDE, K, n_chunks, device)
+    a = (d_ptrs.data_ptr(), d_w.data_ptr(), K, chunks.data_ptr(), n_chunks, z.data_ptr(), out.data_ptr(),
+         work.data_ptr(), work.numel(), 0, nat.stream_handle())
+    if dtype == torch.float32:
+        nat.check(nat.lib().fedagg_wsum_dist2_wide_f32(*a), "wsum_dist2_wide")
+    else:
+        nat.check(nat.lib().fedagg_wsum_dist2_wide_16(_PAIR16_DT[dtype], *a), "wsum_dist2_wide_16")
+    return out
+
+
+def _wsum_dist2_by_count(wide: bool, K: int):
+    """The fused pass for K clients still alive: the wide kernel above
+    GEOMED_MAX_CLIENTS (method "fused_wide" only), the narrow one otherwise."""
+    return wsum_dist2_rows_wide if wide and K > GEOMED_MAX_CLIENTS else wsum_dist2_rows
 
 
 def weiszfeld_step_unfused(d_ptrs: torch.Tensor, d_w, K: int, N: int, chunks: torch.Tensor, n_chunks: int,
@@ -1395,7 +1448,13 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
     fedagg_wsum_dist2_f32 launch ("fused", up to 128 clients) or fedagg_wsum_f32
     + fedagg_dist2_f32 ("unfused"); "auto" takes the fused kernel where it was
     measured faster (GEOMED_AUTO_FUSED) and the pair elsewhere and above 128
-    clients.  One K-double device-to-host copy per pass, as Krum's.
+    clients.  "fused_wide" is the fused pass for up to 1024 clients: a pass
+    over more than 128 live clients is one fedagg_wsum_dist2_wide_f32 launch
+    (_16 for a 16-bit model, whose rows then stay 16-bit at every K: no fp32
+    copy of the clients), a pass over 128 or fewer, after the screen or from
+    the start, the narrow kernel.  "auto" never takes the wide kernel
+    (tools/geomed_wide_probe.py, NOTES.md 7b hold what it measured).  One
+    K-double device-to-host copy per pass, as Krum's.
 
     All-bf16 and all-f16 models (integer buffers allowed) are taken too when
     the clients' tensors are on the device; host dicts of a 16-bit model stay
@@ -1418,8 +1477,8 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
     OrderedDict in client 0's key order on the inputs' device (integer keys
     come back fp32); no client dict is modified.  return_info: also the
     GeomedInfo."""
-    if method not in ("auto", "fused", "unfused"):
-        raise ValueError(f"geomed method {method!r}: 'auto', 'fused' or 'unfused'")
+    if method not in ("auto", "fused", "unfused", "fused_wide"):
+        raise ValueError(f"geomed method {method!r}: 'auto', 'fused', 'unfused' or 'fused_wide'")
     K = len(raw_client_grad_list)
     if K < 1:
         raise ValueError("geomed: no clients")
@@ -1432,20 +1491,23 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
         return (OrderedDict(), GeomedInfo(0, [], np.array(a), (), method)) if return_info else OrderedDict()
     if method == "fused" and K > GEOMED_MAX_CLIENTS:
         raise ValueError(f"the fused Weiszfeld kernel holds at most {GEOMED_MAX_CLIENTS} clients (K = {K})")
+    wide = method == "fused_wide"
+    if wide and K > GEOMED_WIDE_MAX_CLIENTS:
+        raise ValueError(f"the wide fused Weiszfeld kernel holds at most {GEOMED_WIDE_MAX_CLIENTS} clients (K = {K})")
     _one_device(dicts[0], keys, "geomed")
     on_dev = dicts[0][keys[0]].is_cuda
     # 16-bit rounds are taken from device-resident clients (the rows are laid
     # out where the updates already are); host dicts of a 16-bit model stay
     # refused by _float_bucket below, with its message
     row16 = _geomed_row16(dicts[0][k].dtype for k in keys) if on_dev else None
-    if row16 is not None and K <= GEOMED_MAX_CLIENTS and \
-            (method == "fused" or (method == "auto" and geomed16_auto(row16, K))):
-        out, info = _geometric_median16(dicts, keys, row16, a, nu, maxiter, ftol, device)
+    if row16 is not None and (wide or (K <= GEOMED_MAX_CLIENTS and (
+            method == "fused" or (method == "auto" and geomed16_auto(row16, K))))):
+        out, info = _geometric_median16(dicts, keys, row16, a, nu, maxiter, ftol, device, wide)
         return (out, info) if return_info else out
     # a 16-bit model that does not take the 16-bit kernel is widened exactly
     # into the fp32 bucket; anything else but fp32 is refused there
     bucket, dev = _float_bucket(dicts[0], K, "geomed", device, widen=row16)
-    fused = method == "fused" or (method == "auto" and geomed_auto_fused(K))
+    fused = wide or method == "fused" or (method == "auto" and geomed_auto_fused(K))
     with torch.cuda.device(dev):
         for i, d in enumerate(dicts):
             _put_float(bucket, i, d, keys)
@@ -1468,7 +1530,7 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
             def step(w32):
                 d_w = kn.weights_for(w32, torch.float32, dev)
                 if fused:
-                    D = wsum_dist2_rows(ptrs, d_w, Ka, chunks, n_chunks, z, dev)
+                    D = _wsum_dist2_by_count(wide, Ka)(ptrs, d_w, Ka, chunks, n_chunks, z, dev)
                 else:
                     D = weiszfeld_step_unfused(ptrs, d_w, Ka, g.length, chunks, n_chunks, z, dev, aligned=True)
                 return z, D.cpu().numpy()
@@ -1478,7 +1540,7 @@ def geometric_median(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], nu
             return dist2_rows(g.d_ptrs, K, None, chunks, n_chunks, dev).cpu().numpy()
 
         _, w, info, alive = geometric_median_screened(make_step, norms2, a, nu, maxiter, ftol)
-        info.method = "fused" if fused else "unfused"
+        info.method = "fused_wide" if wide else "fused" if fused else "unfused"
         row = z
         others = any(n > 0 and not is_weight_param(k) for k, n in zip(g.keys, g.numels))
         if fused and others:
@@ -1557,12 +1619,18 @@ def _subgroup(g, keep):
                                  numels=[g.numels[j] for j in sel], shapes=[g.shapes[j] for j in sel])
 
 
-def _geometric_median16(dicts, keys, row16: torch.dtype, a, nu: float, maxiter: int, ftol: float, device):
+def _geometric_median16(dicts, keys, row16: torch.dtype, a, nu: float, maxiter: int, ftol: float, device,
+                        wide: bool = False):
     """geometric_median for an all-bf16 / all-f16 model of up to
-    GEOMED_MAX_CLIENTS clients on rows that stay 16-bit on the card (laid out
+    GEOMED_MAX_CLIENTS clients (wide, method "fused_wide": up to
+    GEOMED_WIDE_MAX_CLIENTS, a pass over more than GEOMED_MAX_CLIENTS live
+    clients being one fedagg_wsum_dist2_wide_16 launch) on rows that stay
+    16-bit on the card (laid out
     as coordinate_wise_trimmed_mean lays a 16-bit model out: the float keys'
     16-bit row, integer buffers in an fp32 row as fl32(v)).  Every pass is one
-    fedagg_wsum_dist2_16 launch; the iterate is fp32 throughout.  The result
+    fedagg_wsum_dist2_16 launch; the iterate is fp32 throughout.  (The integer
+    buffers sit in compact fp32 rows beside the bucket, not in a padded row
+    group of it.)  The result
     row is one fedagg_wsum_bf16 / _f16 pass in FEDAGG_ACC_FP32 mode with the
     final weights: the same chain rounded once, rne(z) at the weight columns,
     BatchNorm statistics with the same weights; the integer row one
@@ -1572,11 +1640,26 @@ def _geometric_median16(dicts, keys, row16: torch.dtype, a, nu: float, maxiter: 
     dev = t0.device if t0.is_cuda else (torch.device(device) if device is not None else
                                         torch.device("cuda", torch.cuda.current_device()))
     with torch.cuda.device(dev):
-        bucket = ClientBucket([(k, tuple(dicts[0][k].shape), dicts[0][k].dtype) for k in keys], K, dev)
+        fkeys = [k for k in keys if dicts[0][k].dtype == row16]
+        bucket = ClientBucket([(k, tuple(dicts[0][k].shape), row16) for k in fkeys], K, dev)
         for i, d in enumerate(dicts):
-            _put_float(bucket, i, d, keys)
+            _put_float(bucket, i, d, fkeys)
         bucket.sync_ingest()
         g = bucket.groups[row16]
+        # The integer buffers (a few counters) as fl32(v) in compact fp32 rows
+        # of their own, 16 bytes apart at the least: a bucket row group pads
+        # every client's to 256 bytes, most of a small model's footprint.
+        ig = types.SimpleNamespace(keys=[k for k in keys if dicts[0][k].dtype != row16], offsets=[], numels=[],
+                                   shapes=[], length=0)
+        for k in ig.keys:
+            ig.offsets.append(ig.length)
+            ig.numels.append(dicts[0][k].numel())
+            ig.shapes.append(tuple(dicts[0][k].shape))
+            ig.length += ig.numels[-1]
+        ints = torch.zeros((K, (ig.length + 3) // 4 * 4), dtype=torch.float32, device=dev)
+        for i, d in enumerate(dicts):
+            for k, o, n in zip(ig.keys, ig.offsets, ig.numels):
+                ints[i, o:o + n] = d[k].reshape(-1)  # torch's rounding of int64 -> float32, as put()'s
         chunks, n_chunks = weight_chunks(g, nat.DIST_CHUNK, dev)
         z = torch.zeros(g.padded, dtype=torch.float32, device=dev)
         tables = {}
@@ -1593,7 +1676,8 @@ def _geometric_median16(dicts, keys, row16: torch.dtype, a, nu: float, maxiter: 
 
             def step(w32):
                 d_w = kn.weights_for(w32, torch.float32, dev)
-                return z, wsum_dist2_rows(ptrs, d_w, Ka, chunks, n_chunks, z, dev, dtype=row16).cpu().numpy()
+                step_rows = _wsum_dist2_by_count(wide, Ka)
+                return z, step_rows(ptrs, d_w, Ka, chunks, n_chunks, z, dev, dtype=row16).cpu().numpy()
             return step
 
         def norms2():
@@ -1605,13 +1689,16 @@ def _geometric_median16(dicts, keys, row16: torch.dtype, a, nu: float, maxiter: 
             return n2.cpu().numpy()
 
         _, w, info, alive = geometric_median_screened(make_step, norms2, a, nu, maxiter, ftol)
-        info.method = "fused"
+        info.method = "fused_wide" if wide else "fused"
         d_w = kn.weights_for([float(np.float32(w[i])) for i in alive], torch.float32, dev)
-        rows = []
-        for gr in bucket.groups.values():  # the 16-bit row rounded once from the fp32 chain; the integer keys' fp32 row
-            row = torch.empty(gr.padded, dtype=gr.dtype, device=dev)
-            kn.wsum_ptrs(gr.dtype, table(gr, alive), d_w, len(alive), gr.length, row, True, kn.ACC_FP32)
-            rows.append((gr, row))
+        row = torch.empty(g.padded, dtype=row16, device=dev)  # the 16-bit row rounded once from the fp32 chain
+        kn.wsum_ptrs(row16, table(g, alive), d_w, len(alive), g.length, row, True, kn.ACC_FP32)
+        rows = [(g, row)]
+        if ig.length:  # the integer keys' fp32 row
+            irow = torch.empty(ints.shape[1], dtype=torch.float32, device=dev)
+            kn.wsum_ptrs(torch.float32, kn.upload_i64([ints[i].data_ptr() for i in alive], dev), d_w, len(alive),
+                         ig.length, irow, True, kn.ACC_FP32)
+            rows.append((ig, irow))
         return _rows_to_dict(rows, keys, t0.is_cuda, clone=True), info
 
 

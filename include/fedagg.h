@@ -761,6 +761,51 @@ int fedagg_wsum_dist2_16(int32_t dtype, const void* const* d_src, const float* d
                          double* d_work, int64_t work_len,
                          uint32_t flags, fedagg_stream_t stream);
 
+/* fedagg_wsum_dist2_f32 and fedagg_wsum_dist2_16 for
+ * 1 <= K <= FEDAGG_GEOMED_WIDE_MAX_CLIENTS (csrc/geomed_wide.hip): one pass
+ * per Weiszfeld iteration where a column's K values no longer fit one lane.
+ * P = 2, 4 or 8 adjacent lanes share a column (K <= 256, 512, 1024), each
+ * holding 128 of its slots in registers; the chain crosses the lanes in P
+ * phases and the distances are reduced over the lanes that hold the same
+ * slots.  The contract is the narrow calls' word for word:
+ *   d_z[e], every table column e: acc = fl32(x_0[e] * w_0);
+ *     acc = fl32(acc + fl32(x_i[e] * w_i)), clients in order, never an FMA:
+ *     bit-identical to fedagg_wsum_f32 on the same (widened) rows, a column of
+ *     -0 and subnormals included.  16-bit elements are widened exactly as they
+ *     load; d_z is an fp32 row.
+ *   d_dist2[i] = sum over the table columns of (double)fl32(x_i[e] - d_z[e])^2,
+ *     exact squares summed in fp64 in a fixed order (per-block partials in
+ *     d_work, a fixed-order finish, no atomics): two calls on the same inputs
+ *     give the same bits.
+ * Chunk table as for the narrow calls ((start, length) pairs, 1 <= length <=
+ * FEDAGG_DIST_CHUNK, starts of any alignment); nothing outside the table's
+ * columns is read or written.  A 16-bit chunk whose start is even loads
+ * dwords (two columns a lane group) when every row pointer is 4-byte aligned,
+ * and 2-byte elements otherwise, with the same bits in d_z.  d_w: K DEVICE
+ * floats; FEDAGG_HOST_WEIGHTS is FEDAGG_EINVAL here (the kernel arguments
+ * carry 128 weights).  d_work: fedagg_robust_work_len(
+ * FEDAGG_WORK_WSUM_DIST2_WIDE, K, n_chunks) doubles (K doubles per chunk
+ * group; -1 there for K > 1024; FEDAGG_WORK_WSUM_DIST2's values are what they
+ * were); a smaller one is accepted down to K doubles and runs fewer chunk
+ * groups.  n_chunks == 0: d_dist2 = 0, d_z untouched.  Stream-ordered;
+ * allocates nothing and does not synchronise.  FEDAGG_EINVAL (checked before
+ * any HIP call) for K < 1, n_chunks < 0, a null pointer, work_len < K,
+ * FEDAGG_HOST_WEIGHTS, or a dtype other than FEDAGG_DT_BF16 / FEDAGG_DT_F16 in
+ * the _16 call; FEDAGG_ENOKERNEL for K > FEDAGG_GEOMED_WIDE_MAX_CLIENTS.  The
+ * narrow entry points keep refusing K > FEDAGG_GEOMED_MAX_CLIENTS. */
+#define FEDAGG_GEOMED_WIDE_MAX_CLIENTS 1024
+#define FEDAGG_WORK_WSUM_DIST2_WIDE 9
+int fedagg_wsum_dist2_wide_f32(const float* const* d_src, const float* d_w, int32_t K,
+                               const int64_t* d_chunks, int64_t n_chunks,
+                               float* d_z, double* d_dist2,
+                               double* d_work, int64_t work_len,
+                               uint32_t flags, fedagg_stream_t stream);
+int fedagg_wsum_dist2_wide_16(int32_t dtype, const void* const* d_src, const float* d_w, int32_t K,
+                              const int64_t* d_chunks, int64_t n_chunks,
+                              float* d_z, double* d_dist2,
+                              double* d_work, int64_t work_len,
+                              uint32_t flags, fedagg_stream_t stream);
+
 /* The clipped rebuild of NormDiffClippingDefense (:38-54): over the first N
  * columns of every row,
  *   d_dst_i[e] = fl32( fl32( fl32(src_i[e] - ref[e]) / d_div[i] ) + ref[e] )
