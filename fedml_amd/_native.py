@@ -124,6 +124,7 @@ SIGNATURES = {
     "fedagg_dotnorm2_16": (ctypes.c_int, [_I32, _P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_wsum_diff_16": (ctypes.c_int, [_I32, _P, _P, _I32, _P, _I64, _P, _P]),
     "fedagg_histgram_f32": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),
+    "fedagg_histgram_16": (ctypes.c_int, [_I32, _P, _I32, _P, _P, _P, _I64, _P, _P, _I64, _P]),
     "fedagg_last_error": (ctypes.c_char_p, []),
     "fedagg_version": (_I32, []),
 }

@@ -117,7 +117,14 @@ that are pure reductions over the client axis.
                 pairdist2_rows about a zero centre and dist2_rows.  K^2
                 doubles on the host give each client's weight alpha_i, then
                 global + sum c_i (x_i - global) over EVERY key for the clients
-                with alpha_i > 0 (fedagg_wsum_diff_f32).
+                with alpha_i > 0 (fedagg_wsum_diff_f32).  An all-bf16 or
+                all-f16 model of device-resident clients stays 16-bit on the
+                card while the histories stay fp32: the one pass is
+                fedagg_histgram_16 (the rows widened exactly in registers, then
+                the fp32 kernel's operations; "auto" where HISTGRAM16_AUTO
+                says so), the composed path widens each segment's update, and
+                the rebuild is fedagg_wsum_diff_16; its integer buffers ride
+                in an fp32 row of their own.
 
 "krum", "multikrum"
                 KrumDefense.defend_before_aggregation (krum_defense.py:28-60):
@@ -175,8 +182,10 @@ iterate and one final rounding either way); wise_bulyan takes all-bf16 /
 all-f16 models from host or device dicts (both stages on the 16-bit rows, the
 window's fp32 mean rounded once); fltrust takes all-bf16 / all-f16 models of
 device-resident clients (fedagg_dotnorm2_16 and fedagg_wsum_diff_16 on the
-16-bit rows, the rebuild's fp32 chain rounded once); foolsgold_cos, cclip and
-norm_diff_clipping remain fp32-only.
+16-bit rows, the rebuild's fp32 chain rounded once); foolsgold_cos takes them
+on the same terms (fedagg_histgram_16 or the composed update on the 16-bit
+rows, fp32 histories, fedagg_wsum_diff_16); cclip and norm_diff_clipping remain
+fp32-only.
 """
 from __future__ import annotations
 
@@ -1948,9 +1957,9 @@ def fltrust(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mode
     return (out, info) if return_info else out
 
 
-# ---- FoolsGold (csrc/histgram.hip) ----------------------------------------------
+# ---- FoolsGold (csrc/histgram.hip; csrc/histgram16.hip: 16-bit client rows) ------
 
-HISTGRAM_MAX_CLIENTS = GRAM_MAX_CLIENTS  # fedagg_histgram_f32 holds up to 128 clients
+HISTGRAM_MAX_CLIENTS = GRAM_MAX_CLIENTS  # fedagg_histgram_f32 / fedagg_histgram_16 hold up to 128 clients
 # Whether foolsgold's "auto" runs the fused kernel up to 128 clients, by
 # PAIRGRAM_WIDE_AUTO's rule: True only if the composed path's median time
 # exceeds the fused kernel's by more than the larger min-max spread of the two
@@ -1970,36 +1979,69 @@ def histgram_auto(K: int) -> bool:
     return _tier_auto(HISTGRAM_AUTO, HISTGRAM_MAX_CLIENTS, K)
 
 
+# Whether foolsgold's "auto" runs fedagg_histgram_16 on a bf16 / f16 model up to
+# 128 clients, by the same rule against the composed 16-bit path (the torch
+# update widening each segment, then the fp32 kernels on the histories), which
+# is what "auto" runs otherwise.  An entry is False until measured
+# (tools/foolsgold16_probe.py -> profiles/foolsgold16_probe.json, NOTES.md §5c, §7d).
+# Measured at 4,194,304 columns, the legs launched alternately on the same rows
+# and histories (restored before every launch), median of 10 (min - max),
+# composed / fused:
+#   bf16 K = 128  3.99 (3.97 - 4.08) / 1.04 (1.03 - 1.05) ms: gap 2.94 > 0.11;
+#        K = 100  3.45 (3.44 - 3.49) / 0.91 (0.91 - 0.93): gap 2.54 > 0.05
+#   f16  K = 128  3.99 (3.97 - 4.06) / 1.04 (1.03 - 1.06): gap 2.95 > 0.09;
+#        K = 100  3.44 (3.42 - 3.52) / 0.91 (0.90 - 0.95): gap 2.53 > 0.10
+# (3.8x).  Against fedagg_histgram_f32 on a widened fp32 copy of the same rows
+# (1.19 ms at K = 128, 0.98 at K = 100; the copy itself not timed) the 16-bit
+# kernel takes 0.87x and 0.93x the time, where its bytes are 10 / 12 = 0.83x: the
+# 16-bit loads save time of their own, beside the 4 K N-byte copy that is never
+# made.  Its Gram equals the fp32 kernel's on the widened copy bit for bit.
+HISTGRAM16_AUTO = {torch.bfloat16: {128: True}, torch.float16: {128: True}}
+
+
+def histgram16_auto(dtype: torch.dtype, K: int) -> bool:
+    """Whether foolsgold's "auto" runs fedagg_histgram_16 for K clients of a
+    bf16 / f16 model."""
+    return _tier_auto(HISTGRAM16_AUTO[dtype], HISTGRAM_MAX_CLIENTS, K)
+
+
 def histgram_rows(d_ptrs: torch.Tensor, K: int, ref: torch.Tensor, hist_ptrs: "torch.Tensor | None",
                   chunks: torch.Tensor, n_chunks: int, device) -> torch.Tensor:
     """The K x K fp64 Gram of a_i = fl(fl(x_i - ref) + h_i) over the chunked
-    columns of K <= 128 fp32 device rows, with a_i stored back into the history
-    rows (fedagg_histgram_f32, one pass).  hist_ptrs: the device table of the K
-    history rows' pointers, or None for a_i = fl(x_i - ref) and no store."""
+    columns of K <= 128 device rows, with a_i stored back into the fp32 history
+    rows, in one pass.  fp32 rows: fedagg_histgram_f32; bf16 / f16 rows (the
+    rows' dtype is ref's): fedagg_histgram_16, the same operations on the
+    exactly widened values.  TypeError for any other dtype.  hist_ptrs: the
+    device table of the K history rows' pointers, or None for
+    a_i = fl(x_i - ref) and no store."""
     kn._require_cuda(ref, "histgram")
-    if ref.dtype != torch.float32:
-        raise TypeError("histgram: fp32 rows")
+    if ref.dtype != torch.float32 and ref.dtype not in _FLTRUST16_DT:
+        raise TypeError(f"histgram: fp32, bf16 or f16 rows (ref {ref.dtype})")
     if K > HISTGRAM_MAX_CLIENTS:
         raise ValueError(f"the fused history-Gram kernel holds at most {HISTGRAM_MAX_CLIENTS} clients (K = {K})")
     out = torch.empty((K, K), dtype=torch.float64, device=device)
     work = _work(nat.WORK_HISTGRAM, K, n_chunks, device)
-    nat.check(nat.lib().fedagg_histgram_f32(d_ptrs.data_ptr(), K, ref.data_ptr(),
-                                            hist_ptrs.data_ptr() if hist_ptrs is not None else None,
-                                            chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(),
-                                            work.numel(), nat.stream_handle()), "histgram")
+    args = (d_ptrs.data_ptr(), K, ref.data_ptr(), hist_ptrs.data_ptr() if hist_ptrs is not None else None,
+            chunks.data_ptr(), n_chunks, out.data_ptr(), work.data_ptr(), work.numel(), nat.stream_handle())
+    if ref.dtype == torch.float32:
+        nat.check(nat.lib().fedagg_histgram_f32(*args), "histgram")
+    else:
+        nat.check(nat.lib().fedagg_histgram_16(_FLTRUST16_DT[ref.dtype], *args), "histgram_16")
     return out
 
 
 def histgram_rows_torch(rows, ref, hist=None, cols=None) -> torch.Tensor:
-    """The specification of fedagg_histgram_f32 in torch ops, on any device.
-    rows: a (K, N) fp32 tensor or a list of K rows; hist: the same of history
-    rows, updated IN PLACE on the columns that count, or None; cols: index
-    tensor of those columns (None: all).  a_i = (x_i - ref) + h_i, two fp32
-    roundings; returns the K x K float64 Gram of the a_i: exact products (two
-    fp32 values multiply exactly in fp64), fp64 sums in torch's order."""
+    """The specification of fedagg_histgram_f32 / fedagg_histgram_16 in torch
+    ops, on any device.  rows: a (K, N) tensor or a list of K rows, fp32, or
+    bf16 / f16 (widened exactly first, ref with them); hist: the same of fp32
+    history rows, updated IN PLACE on the columns that count, or None; cols:
+    index tensor of those columns (None: all).  a_i = (x_i - ref) + h_i, two
+    fp32 roundings; returns the K x K float64 Gram of the a_i: exact products
+    (two fp32 values multiply exactly in fp64), fp64 sums in torch's order."""
     K = len(rows)
+    ref = ref.float()
     rc = ref if cols is None else ref[cols]
-    A = torch.stack([(rows[i] if cols is None else rows[i][cols]) - rc for i in range(K)])
+    A = torch.stack([(rows[i] if cols is None else rows[i][cols]).float() - rc for i in range(K)])
     if hist is not None:
         for i in range(K):
             A[i] = A[i] + (hist[i] if cols is None else hist[i][cols])
@@ -2032,12 +2074,15 @@ def histgram_rows_composed(x_rows: torch.Tensor, ref: torch.Tensor, hist: torch.
     any K: the history update in torch ops (histgram_rows_torch's, bit for
     bit), then G_ij = (n_i + n_j - D_ij) / 2 from the histories' squared
     distances (pairdist2_rows, "auto" about a zero centre) and squared norms
-    n_i (dist2_rows), G_ii = n_i.  x_rows: (K, P) fp32; hist: the state's (R, P)
-    row tensor; sel: the K history rows' indices in it (None: the first K);
-    hist_ptrs: their pointer table; segs: weight_segments; zero: a zero fp32
-    row of P columns (made here when None)."""
+    n_i (dist2_rows), G_ii = n_i.  x_rows: (K, P) fp32, or bf16 / f16 with ref
+    (each segment's update widens them exactly first, so the histories get the
+    specification's values bit for bit; everything after the update runs on the
+    fp32 histories); hist: the state's (R, P) fp32 row tensor; sel: the K
+    history rows' indices in it (None: the first K); hist_ptrs: their pointer
+    table; segs: weight_segments; zero: a zero fp32 row of P columns (made
+    here when None)."""
     for off, n in segs:
-        upd = x_rows[:K, off:off + n] - ref[off:off + n]
+        upd = x_rows[:K, off:off + n].float() - ref[off:off + n].float()
         if sel is None:
             hist[:K, off:off + n] += upd  # fl(h + u) = fl(u + h)
         else:
@@ -2109,11 +2154,14 @@ def foolsgold_weights(G, confidence: float = 1.0) -> Tuple[np.ndarray, np.ndarra
 
 class FoolsGoldState:
     """The server's memory for "foolsgold_cos": one fp32 device row per client
-    ever seen, the sum of its updates so far, laid out like the clients' fp32
-    bucket rows (the group's padded columns; only the weight keys' columns are
-    ever written), zero-filled.  Created empty; the first round binds it to
-    that round's layout and device, and a later round with another layout or
-    device raises ValueError.  Capacity grows by doubling."""
+    ever seen, the sum of its updates so far, laid out like the clients'
+    bucket rows of the float keys (the group's padded columns; only the weight
+    keys' columns are ever written), zero-filled.  The histories are fp32 rows
+    whatever the model's dtype; a bf16 / f16 model's group has other element
+    offsets than an fp32 model's, and its dtype is part of the bound layout.
+    Created empty; the first round binds it to that round's layout, dtype and
+    device, and a later round with another one raises ValueError.  Capacity
+    grows by doubling."""
 
     def __init__(self):
         self.rows: "torch.Tensor | None" = None
@@ -2122,7 +2170,7 @@ class FoolsGoldState:
         self.device = None
 
     def bind(self, group, device) -> None:
-        layout = (tuple(group.keys), tuple(group.offsets), tuple(group.numels), int(group.rows.shape[1]))
+        layout = (tuple(group.keys), tuple(group.offsets), tuple(group.numels), int(group.rows.shape[1]), group.dtype)
         if self.layout is None:
             self.layout, self.device = layout, torch.device(device)
         elif layout != self.layout or torch.device(device) != self.device:
@@ -2189,10 +2237,24 @@ def foolsgold(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mo
 
     A client whose history came out non-finite (it sent a NaN or an inf) is
     reset after the round.  fp32 models (integer buffers allowed, entering as
-    fl32(v) and coming back fp32).  KeyError for a key of client 0 missing from
-    another client or from global_model.  Returns a new OrderedDict in client
-    0's key order on the inputs' device; no input is modified.  return_info:
-    also the FoolsGoldInfo."""
+    fl32(v) and coming back fp32), and all-bf16 or all-f16 models of
+    device-resident clients, whose float keys stay one 16-bit row group on the
+    card while the histories stay fp32: step 1 is fedagg_histgram_16 ("fused";
+    "auto" where HISTGRAM16_AUTO says so) or histgram_rows_composed widening
+    each segment's update (any K), the fp32 operations on the exactly widened
+    values either way, and step 3 one fedagg_wsum_diff_16 pass, its fp32 chain
+    rounded once to the model's dtype.  Their int64 / int32 / bool buffers
+    form an fp32 row group as fl32(v), rebuilt by fedagg_wsum_diff_f32 with
+    the same coefficients over the same included clients (float keys come back
+    in the model's dtype, integer keys fp32); an integer tensor under a
+    weight-key name is refused (it would sit outside the histories' rows), and
+    so is a global_model whose key dtypes differ from client 0's (TypeError).
+    Host dicts of a 16-bit model and mixed-width float models are refused.  A
+    state started on an fp32 model refuses a 16-bit round, and the reverse
+    (ValueError).  KeyError for a key of client 0 missing from another client
+    or from global_model.  Returns a new OrderedDict in client 0's key order
+    on the inputs' device; no input is modified.  return_info: also the
+    FoolsGoldInfo."""
     K = len(raw_client_grad_list)
     if K < 1:
         raise ValueError("foolsgold: no clients")
@@ -2208,24 +2270,46 @@ def foolsgold(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mo
                          f"'composed' serves any K")
     if not isinstance(state, FoolsGoldState):
         raise TypeError("foolsgold: state must be a FoolsGoldState")
-    fused = method == "fused" or (method == "auto" and histgram_auto(K))
     dicts, keys = _client_dicts(raw_client_grad_list)
     for k in keys:
-        global_model[k]
+        cdt, gdt = dicts[0][k].dtype, global_model[k].dtype
+        if cdt != gdt and (cdt in _FLTRUST16_DT or gdt in _FLTRUST16_DT):  # put() would round or widen one of them
+            raise TypeError(f"foolsgold: global_model[{k!r}] is {gdt}, client 0's is {cdt}; the global model of a "
+                            f"bf16 / f16 round has the clients' dtypes, and an fp32 round takes no 16-bit one")
+    on_dev = bool(keys) and dicts[0][keys[0]].is_cuda
+    row_dt = _bulyan_row16(dicts[0], keys) if on_dev else None
+    if row_dt is None:
+        fused = method == "fused" or (method == "auto" and histgram_auto(K))
+    else:
+        fused = method == "fused" or (method == "auto" and histgram16_auto(row_dt, K))
     if not keys:
         info = FoolsGoldInfo(np.zeros(K), np.zeros((K, K)), np.zeros(K), "fused" if fused else "composed")
         return (OrderedDict(), info) if return_info else OrderedDict()
     _one_device(dicts[0], keys, "foolsgold")
-    on_dev = dicts[0][keys[0]].is_cuda
-    bucket, dev = _float_bucket(dicts[0], K, "foolsgold", device)
-    gb, _ = _float_bucket(dicts[0], 1, "foolsgold", dev)  # the global model, laid out like the clients
+    if row_dt is None:  # fp32 models; everything else is refused there, with its message
+        row_dt = torch.float32
+        bucket, dev = _float_bucket(dicts[0], K, "foolsgold", device)
+        gb, _ = _float_bucket(dicts[0], 1, "foolsgold", dev)  # the global model, laid out like the clients
+    else:
+        for k in keys:
+            if is_weight_param(k) and not dicts[0][k].is_floating_point():
+                raise NotImplementedError(
+                    f"foolsgold: key {k!r} is an integer tensor ({dicts[0][k].dtype}) under a weight-key name; in a "
+                    f"{row_dt} model the histories run over the {row_dt} rows, which it would not be part of")
+            if global_model[k].dtype != dicts[0][k].dtype:  # put() would round an fp32 model into the 16-bit row
+                raise TypeError(f"foolsgold: global_model[{k!r}] is {global_model[k].dtype}, client 0's is "
+                                f"{dicts[0][k].dtype}; in a {row_dt} round the global model has the clients' dtypes")
+        dev = dicts[0][keys[0]].device
+        layout = [(k, tuple(dicts[0][k].shape), dicts[0][k].dtype) for k in keys]
+        with torch.cuda.device(dev):
+            bucket, gb = ClientBucket(layout, K, dev), ClientBucket(layout, 1, dev)
     with torch.cuda.device(dev):
         for i, d in enumerate(dicts):
             _put_float(bucket, i, d, keys)
         _put_float(gb, 0, global_model, keys)
         bucket.sync_ingest()
         gb.sync_ingest()
-        g, ref = bucket.groups[torch.float32], gb.groups[torch.float32].rows[0]
+        g, ref = bucket.groups[row_dt], gb.groups[row_dt].rows[0]  # the float keys: an fp32 model's only group
         state.bind(g, dev)
         sel = state.rows_for(ids)
         chunks, n_chunks = weight_chunks(g, nat.PAIR_CHUNK, dev)
@@ -2247,12 +2331,17 @@ def foolsgold(raw_client_grad_list: List[Tuple[float, "OrderedDict"]], global_mo
         if not incl:
             logging.warning("foolsgold: every client's weight is 0 (each is another's copy, or non-finite); "
                             "the global model is kept")
-        row = torch.empty(g.rows.shape[1], dtype=torch.float32, device=dev)
         Ki = len(incl)
-        i_ptrs = kn.upload_i64([g.rows[i].data_ptr() for i in incl], dev) if Ki else None
         d_c = kn.upload_f32([float(c32[i]) for i in incl], dev) if Ki else None
-        wsum_diff_rows(i_ptrs, d_c, Ki, ref, g.length, row)
-        out = _rows_to_dict([(g, row)], keys, on_dev, clone=True)
+
+        def rows():  # a 16-bit model's integer buffers are a second, fp32 group: the same coefficients
+            for dt, gr in bucket.groups.items():
+                row = torch.empty(gr.rows.shape[1], dtype=dt, device=dev)
+                i_ptrs = kn.upload_i64([gr.rows[i].data_ptr() for i in incl], dev) if Ki else None
+                wsum_diff_rows(i_ptrs, d_c, Ki, gb.groups[dt].rows[0], gr.length, row)
+                yield gr, row
+
+        out = _rows_to_dict(rows(), keys, on_dev, clone=True)
     coeffs = np.where(alpha > 0, c32.astype(np.float64), 0.0)
     info = FoolsGoldInfo(alpha, cs, coeffs, "fused" if fused else "composed")
     return (out, info) if return_info else out

@@ -18,7 +18,8 @@ the median; FedML's own "bulyan" stays refused), and "fltrust", FLTrust (not in
 FedML: the server hands its root model over with set_fltrust_root before every
 round), and "foolsgold_cos", our FoolsGold (the aggregator keeps the clients'
 update histories across rounds; set_foolsgold_clients names each round's
-clients; FedML's own "foolsgold" stays refused) (all five on
+clients; fp32 models, and all-bf16 / all-f16 models of device-resident clients;
+FedML's own "foolsgold" stays refused) (all five on
 aggregation); so do the distance-based
 "krum" / "multikrum", "norm_diff_clipping", "slsgd" and "cclip".  "robust_learning_rate" and
 "weak_dp" are accepted and, as in FedML, leave the plugin path a plain FedAvg

@@ -961,6 +961,33 @@ int fedagg_histgram_f32(const float* const* d_src, int32_t K, const float* d_ref
                         double* d_out /* K x K */, double* d_work, int64_t work_len,
                         fedagg_stream_t stream);
 
+/* fedagg_histgram_f32 for bf16 / f16 client rows (csrc/histgram16.hip; dtype
+ * FEDAGG_DT_BF16 or FEDAGG_DT_F16, d_src's rows and d_ref of that type): an
+ * all-bf16 or all-f16 model's round of "foolsgold_cos" with the clients left
+ * 16-bit on the card.  The history rows are fp32 (an accumulated sum) and are
+ * updated in place.  With w the exact widening of a 16-bit value to fp32, for
+ * every column e of the chunk table and every client i < K, 1 <= K <= 128:
+ *   a_i[e] = fl32( fl32(w(src_i[e]) - w(d_ref[e])) + d_hist[i][e] ),
+ *   d_hist[i][e] = a_i[e]
+ *   d_out[i*K + j] = sum_e a_i[e] a_j[e]       (fp64)
+ * i.e. fedagg_histgram_f32 on the widened rows: the same two roundings, the
+ * same three-way split of a, the same six products, sums, bound (~1e-7 |a_i|
+ * |a_j|), symmetry, treatment of NaN and inf, determinism, chunk table and
+ * workspace (FEDAGG_WORK_HISTGRAM's formula and minimum; there is no work
+ * kind of its own).  d_hist == NULL: a_i[e] = fl32(w(src_i[e]) - w(d_ref[e]))
+ * and nothing is stored.  A column outside the table is neither read nor
+ * written.  Rows and d_ref may have any 2-byte alignment and history rows any
+ * 4-byte alignment; the results are the same bits at every alignment (a row
+ * piece on an 8-byte boundary is one 8-byte load, any other is loaded by
+ * element).  n_chunks == 0: d_out = 0.  Stream-ordered; allocates nothing and
+ * does not synchronise.  FEDAGG_EINVAL (checked before any HIP call) for an
+ * unknown dtype and for everything fedagg_histgram_f32 refuses. */
+int fedagg_histgram_16(int32_t dtype, const void* const* d_src, int32_t K, const void* d_ref,
+                       float* const* d_hist /* NULL: no history */,
+                       const int64_t* d_chunks, int64_t n_chunks,
+                       double* d_out /* K x K */, double* d_work, int64_t work_len,
+                       fedagg_stream_t stream);
+
 /* The robust-learning-rate defense (RobustLearningRateDefense.run,
  * core/security/defense/robust_learning_rate_defense.py:35-62, reached through
  * FedMLDefender.defend from simulation/mpi/fedavg/FedAVGAggregator.py:83-88):
