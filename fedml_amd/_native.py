@@ -39,6 +39,9 @@ GEOMED_MAX_CLIENTS = 128  # FEDAGG_GEOMED_MAX_CLIENTS
 GEOMED_WIDE_MAX_CLIENTS = 1024  # FEDAGG_GEOMED_WIDE_MAX_CLIENTS
 NEARMEDIAN_MAX_CLIENTS = 128  # FEDAGG_NEARMEDIAN_MAX_CLIENTS
 NEARMEDIAN_WIDE_MAX_CLIENTS = 1024  # FEDAGG_NEARMEDIAN_WIDE_MAX_CLIENTS
+LCC_VALU, LCC_MFMA = 0, 1  # FEDAGG_LCC_VALU / FEDAGG_LCC_MFMA
+LCC_MAX_DIM = 1024  # FEDAGG_LCC_MAX_DIM
+LCC_MFMA_MAX_PRIME = 65279  # FEDAGG_LCC_MFMA_MAX_PRIME
 # FEDAGG_FEDOPT_*: the launch kinds of fedagg_wsum_fedopt_batch (besides the FEDAGG_OPT_* codes)
 FEDOPT_AVG, FEDOPT_SGD, FEDOPT_ADAM, FEDOPT_ADAMW, FEDOPT_ADAGRAD, FEDOPT_RMSPROP = 0, 16, 17, 18, 19, 20
 
@@ -100,6 +103,8 @@ SIGNATURES = {
     "fedagg_nearmedian_mean_wide_16": (ctypes.c_int, [_I32, _P, _I32, _I64, _I32, _P, _U32, _P]),
     "fedagg_sum_mod_i64": (ctypes.c_int, [_P, _I32, _I64, _I64, _P, _U32, _P]),
     "fedagg_lsa_reconstruct_f32": (ctypes.c_int, [_P, _I32, _I64, _P, _I64, _I32, _F, _P, _U32, _P]),
+    "fedagg_lcc_work_bytes": (_I64, [_I32, _I32, _I64]),
+    "fedagg_lcc_decode_i64": (ctypes.c_int, [_P, _I32, _I64, _P, _I32, _I64, _P, _I64, _I32, _P, _I64, _P]),
     "fedagg_host_pack": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32]),
     "fedagg_host_gather": (ctypes.c_int, [_P, _P, _P, _I32, _I32]),
     "fedagg_host_unpack": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32]),

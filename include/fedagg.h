@@ -1024,6 +1024,49 @@ int fedagg_lsa_reconstruct_f32(const int64_t* const* d_src, int32_t K, int64_t N
                                float w, float* d_out, uint32_t flags,
                                fedagg_stream_t stream);
 
+/* LightSecAgg's mask decode (LCC_decoding_with_points, lightsecagg.py:
+ * (U_dec.dot(f_eval)) % p), a matrix product over the field:
+ *   out[t][n] = floor_mod(Σ_u coef[t][u] · src[u][n], p),  t < R, n < M,
+ * numpy int64 semantics for ANY int64 inputs and any p > 0: products and the
+ * sum wrap modulo 2^64 (so the order is free), the modulo is a floor modulo.
+ * d_src: U device row pointers (the survivors' encoded aggregate masks, M
+ * int64 each); d_coef: R x U int64, row-major, on the device; d_out: the
+ * row-major R x M product, of which only the first n_out elements are written
+ * (0 <= n_out <= R * M; FedML keeps aggregate_mask[0:d]).
+ *
+ * method FEDAGG_LCC_VALU: the exact 64-bit kernel, the specification for every
+ * input; d_work is not read.
+ * method FEDAGG_LCC_MFMA: the int8 matrix cores, for field data.  With
+ * 0 <= every coefficient, every element < p the sum cannot wrap and only its
+ * residue matters, so each value is replaced by its centred representative r,
+ * |r| <= floor(p / 2), split as r = 256 hi + lo with lo the sign-extended low
+ * byte; hi fits a signed byte iff -32896 <= r <= 32639, which holds for
+ * p <= FEDAGG_LCC_MFMA_MAX_PRIME = 2 * 32639 + 1.  Three int32 sums of byte
+ * products (|Σ| <= 2^25 at U = 1024: exact) give the residue.  The result is
+ * still the specification bit for bit for every input: a 64-column tile that
+ * holds an element outside [0, p) is flagged in d_work and computed by the
+ * exact kernel in the same call (no host synchronisation); an out-of-range
+ * coefficient, or p above the bound, sends the whole call to the exact kernel.
+ * d_work: fedagg_lcc_work_bytes(U, R, M) bytes, 16-byte aligned (the
+ * coefficients' byte planes and the tile flags; -1 for sizes the entry point
+ * refuses).
+ *
+ * Stream-ordered; allocates nothing and does not synchronise.  Checked before
+ * any HIP call: FEDAGG_EINVAL for U < 1, R < 1, M < 0, p <= 0, n_out outside
+ * [0, R * M], an unknown method, a null pointer or (FEDAGG_LCC_MFMA, p within
+ * the bound) a d_work that is null, misaligned or too small; FEDAGG_ENOKERNEL
+ * for U or R above FEDAGG_LCC_MAX_DIM.  n_out == 0 is FEDAGG_OK without a
+ * launch. */
+#define FEDAGG_LCC_VALU 0
+#define FEDAGG_LCC_MFMA 1
+#define FEDAGG_LCC_MAX_DIM 1024
+#define FEDAGG_LCC_MFMA_MAX_PRIME 65279
+int64_t fedagg_lcc_work_bytes(int32_t U, int32_t R, int64_t M);
+int fedagg_lcc_decode_i64(const int64_t* const* d_src, int32_t U, int64_t M,
+                          const int64_t* d_coef, int32_t R, int64_t p,
+                          int64_t* d_out, int64_t n_out, int32_t method,
+                          void* d_work, int64_t work_bytes, fedagg_stream_t stream);
+
 /* ---- Host ingest helper -------------------------------------------------- */
 
 /* HOST-side gather of n host buffers into one host buffer (normally pinned
